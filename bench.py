@@ -10,8 +10,13 @@ x 3000 nodes per GPU, the yml graph (k = 10, eps^2 = 25 -> E ~ 37.8k edges per f
 L = 7, **fp32** compute (the reference precision; parity 1e-4), the trained
 checkpoint's weights (`1718175257362`, committed as the `w/*` arrays of
 tests/golden/model_trained_N50.npz -- nothing is read from the reference at run time).
-The same run also times BASELINE config 2 (64 x 3000, k = 32, L = 6, bf16) as the extra
-key ``c2_bf16``.
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line (the
+per-kernel figures in it come from HIP events recorded inside the timed steps).  ``--full``
+adds every measurement that takes a run of its own: the shader-clock probes around the
+timed region, the forward-only loop, the standalone scatter-aggregate kernel, BASELINE
+config 2 (64 x 3000, k = 32, L = 6, bf16) as the extra key ``c2_bf16`` (config m), and the
+CPU baseline.  ``--dump-outputs DIR`` writes what the last timed step returned to
+``DIR/<name>.npy``.
 Multi-GPU (torchrun, one process per GPU): every rank owns its own 64 frames
 (frame-parallel, weak scaling, no collective in the timed region; barrier +
 max-over-ranks timing only).
@@ -106,11 +111,20 @@ def parse():
                         'bf16 for c2, fp16 for c5)')
     p.add_argument('--weights', default=None, choices=['trained', 'random'],
                    help='trained: the checkpoint committed in tests/golden (L = 7 only)')
+    p.add_argument('--full', action='store_true',
+                   help='also run the measurements that take runs of their own: clock probes, '
+                        'the forward-only loop, the standalone scatter-aggregate kernel, the '
+                        'extra BASELINE config 2 (bf16) measurement (m) and the CPU baseline')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='after the timed steps, write what the last timed step returned to '
+                        'DIR/<name>.npy (float32 / float64; at most 64 MB in all, a fixed seeded '
+                        'sample of the rows of larger outputs); ranks > 0 write <name>.rank<r>.npy')
     p.add_argument('--no-extra', action='store_true',
-                   help='m: skip the extra BASELINE config 2 (bf16) measurement')
+                   help='with --full, m: skip the extra BASELINE config 2 (bf16) measurement')
     p.add_argument('--cpu-frames', type=int, default=None,
                    help='CPU baseline sample (timed frames)')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--no-cpu-baseline', action='store_true',
+                   help='with --full: skip the CPU baseline')
     p.add_argument('--fine-events', action='store_true',
                    help='time every launch with its own HIP event pair (adds ~10 us of stream '
                         'gap per pair to the timed steps)')
@@ -612,7 +626,7 @@ def train_main(args, world, rank, local):
         losses, acc, gb = trainer.step(batch, labels)
     torch.cuda.synchronize()
     E = int(gb.n_edges_dev.item())
-    clk0 = clock_probe(dev)
+    clk0 = clock_probe(dev) if args.full else None
     barrier(world)
     torch.cuda.synchronize()
     events = []
@@ -622,7 +636,11 @@ def train_main(args, world, rank, local):
     torch.cuda.synchronize()
     barrier(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world)
-    clock = clock_record(clk0, clock_probe(dev))
+    clock = clock_record(clk0, clock_probe(dev)) if args.full else None
+    if args.dump_outputs:
+        # what the last step returned, and the parameters its update left
+        dump_outputs(args.dump_outputs, rank,
+                     dict(losses=losses, accuracy=acc, parameters=trainer.opt.flat))
     frames_total = sum_over_ranks(args.frames * args.steps, world)
     rank_frames = per_rank_counts(args.frames * args.steps, world)
     durs = event_durations(events)
@@ -666,10 +684,11 @@ def train_main(args, world, rank, local):
         'last_losses': [round(float(x), 5) for x in losses.cpu()],
         'applied_steps': trainer.opt.applied_steps(),
         'roofline': roof,
-        'clock': clock,
     }
-    add_cycles({}, roof, clock)
-    if rank == 0 and not args.no_cpu_baseline:  # after the timed region, every world size
+    if args.full:
+        line['clock'] = clock
+        add_cycles({}, roof, clock)
+    if rank == 0 and args.full and not args.no_cpu_baseline:  # after the timed region
         line['cpu_baseline'] = cpu_train_baseline(args, cfg)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -741,10 +760,12 @@ def cls_main(args, world, rank, local):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step(events)
+            logits = step(events)
         torch.cuda.synchronize()
         barrier(world)
         elapsed = max_over_ranks(time.perf_counter() - t0, world)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, dict(logits=logits))
     durs = event_durations(events)
     objs_total = sum_over_ranks(args.frames * args.nodes * args.steps, world)
     s = 2 if args.dtype == 'bf16' else 4
@@ -780,7 +801,7 @@ def cls_main(args, world, rank, local):
                      'frac': round(tf / peak, 4), 'traffic': None},
         'kernels': kern,
     }
-    if rank == 0 and not args.no_cpu_baseline:  # after the timed region, every world size
+    if rank == 0 and args.full and not args.no_cpu_baseline:  # after the timed region
         line['cpu_baseline'] = cpu_classifier_baseline(args, cfg, sd_cpu)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -825,10 +846,15 @@ def frontend_main(args, world, rank, local):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(events)
+        dd, gd = step(events)
     torch.cuda.synchronize()
     barrier(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world)
+    if args.dump_outputs:
+        # the dynamic frames' data and label dicts the last step returned
+        arrays = {f'data_{k}': v for k, v in dd.items() if isinstance(v, torch.Tensor)}
+        arrays.update({f'labels_{k}': v for k, v in gd.items() if isinstance(v, torch.Tensor)})
+        dump_outputs(args.dump_outputs, rank, arrays)
     durs = event_durations(events)
     total = sum_over_ranks(args.frames * args.steps, world)
     ms = float(np.mean(durs['sync']))
@@ -854,7 +880,7 @@ def frontend_main(args, world, rank, local):
                      'frac': round(gbs / HBM_PEAK_GBS, 4), 'traffic': None,
                      'avg_ms': round(ms, 4), 'bytes_per_launch': nbytes},
     }
-    if rank == 0 and not args.no_cpu_baseline:  # after the timed region, every world size
+    if rank == 0 and args.full and not args.no_cpu_baseline:  # after the timed region
         from oracle import frontend_ref  # the CPU baseline leg only
         sample = wins[:args.cpu_frames]
         t = time.perf_counter()
@@ -912,10 +938,46 @@ def save_rank_outputs(args, rank, seeds, gb, out):
     log(f'rank {rank}: outputs of {F} frame(s) saved to {args.save_outputs}')
 
 
-def gnn_measure(args, world, dev, cfg, sd, scatter=True):
+DUMP_BUDGET_BYTES = 60 * 10**6     # --dump-outputs: under 64 MB in all, headers included
+
+
+def dump_outputs(out_dir, rank, arrays):
+    """--dump-outputs: each of `arrays` (name -> tensor / ndarray / scalar, what the last
+    timed step returned) as out_dir/<name>.npy, float64 kept, everything else as float32
+    (integer arrays as float64: exact up to 2^53).  When the arrays together exceed
+    DUMP_BUDGET_BYTES every array keeps the same fraction of its rows, chosen by a fixed
+    seeded draw (ascending), so two runs with the same arguments dump the same rows."""
+    host = {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            v = v.double() if v.dtype == torch.float64 or not v.is_floating_point() else v.float()
+            v = v.cpu().numpy()
+        else:
+            v = np.asarray(v)
+            v = v.astype(np.float64 if v.dtype == np.float64 or v.dtype.kind in 'iub'
+                         else np.float32)
+        host[name] = np.atleast_1d(v)
+    total = sum(v.nbytes for v in host.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(20240607)
+    for name in sorted(host):
+        v = host[name]
+        if frac < 1.0 and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * frac))
+            v = v[np.sort(rng.choice(v.shape[0], size=keep, replace=False))]
+        suffix = '' if rank == 0 else f'.rank{rank}'
+        np.save(os.path.join(out_dir, f'{name}{suffix}.npy'), np.ascontiguousarray(v))
+    log(f'rank {rank}: {len(host)} output array(s) written to {out_dir}'
+        + ('' if frac == 1.0 else f' (a seeded {frac:.3f} sample of the rows)'))
+
+
+def gnn_measure(args, world, dev, cfg, sd, scatter=True, full=True):
     """Warm up, then time args.steps full steps (barrier + synchronize on both sides,
-    max over ranks), then the forward alone; per-kernel HIP-event durations and the
-    roofline of the conv layer kernel."""
+    max over ranks); per-kernel HIP-event durations of the timed steps and the roofline of
+    the conv layer kernel.  full: also the clock probes around the timed region, the forward
+    alone and (scatter) the standalone scatter-aggregate kernel."""
     from graph_neural_network_for_radar_perception_amd.graph_features import FrameBatch
     from graph_neural_network_for_radar_perception_amd.pipeline import (PipelinedSteps,
                                                                          RadarGNNPipeline)
@@ -949,7 +1011,7 @@ def gnn_measure(args, world, dev, cfg, sd, scatter=True):
         # per step (a pair per launch cost ~10 us of stream gap each); --fine-events
         # times every launch
         events = EventList(coarse=not args.fine_events)
-        clk0 = clock_probe(dev)
+        clk0 = clock_probe(dev) if full else None
         barrier(world)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -958,30 +1020,41 @@ def gnn_measure(args, world, dev, cfg, sd, scatter=True):
         torch.cuda.synchronize()
         barrier(world)
         elapsed = max_over_ranks(time.perf_counter() - t0, world)
-        clock = clock_record(clk0, clock_probe(dev))
+        clock = clock_record(clk0, clock_probe(dev)) if full else None
         if args.streams > 1:
             pipe = stepper.pipes[(stepper.i - 1) % stepper.depth]
         if args.save_outputs:
             save_rank_outputs(args, rank, seeds, gb, out)
+        if args.dump_outputs:
+            # what a caller of the step receives (RadarGNNPipeline.trim) and the link pairs
+            # the link_cls rows belong to
+            U = int(gb.graph.n_pairs_dev.item())
+            names = ('node_cls', 'node_reg', 'link_cls', 'obj_cls')
+            dump_outputs(args.dump_outputs, rank,
+                         dict(zip(names, RadarGNNPipeline.trim(gb, out)),
+                              pair_src=gb.graph.pair_src[:U], pair_dst=gb.graph.pair_dst[:U]))
         durs = event_durations(events)
         if 'conv_stack' in durs:  # per-layer launch time = span / layers
             durs['conv_fused'] = [ms / args.layers for ms in durs.pop('conv_stack')]
-        # ---- forward only (graph + features already built) -----------------------
-        barrier(world)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        ev_iso = EventList(coarse=True)
-        for _ in range(args.steps):
-            pipe.forward(batch, gb, ev_iso)
-        torch.cuda.synchronize()
-        barrier(world)
-        fwd_elapsed = max_over_ranks(time.perf_counter() - t1, world)
-        # the conv stack without a concurrent graph build (the timed steps overlap step i's
-        # build with step i-1's forward when --streams > 1)
-        iso = event_durations(ev_iso).get('conv_stack')
-        iso_ms = float(np.mean(iso)) / args.layers if iso else None
-        sc = (scatter_aggregate_bench(gb, E, args.frames * args.nodes, max(args.steps, 5))
-              if scatter else None)
+        fwd_elapsed, iso_ms, sc = None, None, None
+        if full:
+            # ---- forward only (graph + features already built) -------------------
+            barrier(world)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            ev_iso = EventList(coarse=True)
+            for _ in range(args.steps):
+                pipe.forward(batch, gb, ev_iso)
+            torch.cuda.synchronize()
+            barrier(world)
+            fwd_elapsed = max_over_ranks(time.perf_counter() - t1, world)
+            # the conv stack without a concurrent graph build (the timed steps overlap step
+            # i's build with step i-1's forward when --streams > 1)
+            iso = event_durations(ev_iso).get('conv_stack')
+            iso_ms = float(np.mean(iso)) / args.layers if iso else None
+            if scatter:
+                sc = scatter_aggregate_bench(gb, E, args.frames * args.nodes,
+                                             max(args.steps, 5))
 
     frames_total = sum_over_ranks(args.frames * args.steps, world)
     rank_frames = per_rank_counts(args.frames * args.steps, world)
@@ -1113,12 +1186,15 @@ def gnn_measure(args, world, dev, cfg, sd, scatter=True):
                     algorithmic_bytes=nbytes, traffic_over_algorithmic=round(traffic / nbytes, 3))
     F = (84992.0 * N + 118272.0 * E + args.layers * (65536.0 * E + 16384.0 * N) + 99456.0 * N
          + 33024.0 * (E / 2) + 9088.0 * (N / 5))       # SURVEY §8(d) forward flops
-    fwd_ms = fwd_elapsed / args.steps * 1e3
-    add_cycles(kern, roof, clock)
-    return {'value': frames_total / elapsed, 'elapsed': elapsed, 'ms_step': elapsed / args.steps * 1e3,
-            'forward_fps': frames_total / fwd_elapsed, 'forward_ms': fwd_ms, 'E': E,
-            'forward_tflops': F / (fwd_ms * 1e-3) / 1e12, 'roof': roof, 'kern': kern,
-            'scatter': sc, 'rank_frames': rank_frames, 'clock': clock}
+    r = {'value': frames_total / elapsed, 'elapsed': elapsed, 'ms_step': elapsed / args.steps * 1e3,
+         'E': E, 'roof': roof, 'kern': kern, 'scatter': sc, 'rank_frames': rank_frames,
+         'clock': clock}
+    if full:
+        fwd_ms = fwd_elapsed / args.steps * 1e3
+        add_cycles(kern, roof, clock)
+        r.update(forward_fps=frames_total / fwd_elapsed, forward_ms=fwd_ms,
+                 forward_tflops=F / (fwd_ms * 1e-3) / 1e12)
+    return r
 
 
 def main():
@@ -1141,7 +1217,7 @@ def main():
                          k_number_nearest_points=args.k)
     sd = model_state(cfg, args.weights)
     log(f'config {args.config}, dtype {args.dtype}, weights {args.weights}')
-    r = gnn_measure(args, world, dev, cfg, sd)
+    r = gnn_measure(args, world, dev, cfg, sd, full=args.full)
     log(f'{args.config}: {r["value"]:.1f} frames/s, {r["ms_step"]:.3f} ms/step')
     line = {
         'metric': METRIC, 'value': round(r['value'], 2), 'unit': 'frames/s', 'n_gpus': world,
@@ -1160,19 +1236,24 @@ def main():
                    'streams': args.streams, 'concurrent_forwards': bool(args.concurrent and args.streams > 1),
                    'conv_waves': conv_waves_of(args),
                    'backend': dist.get_backend() if world > 1 else None},
-        'forward_only_frames_per_s': round(r['forward_fps'], 2),
-        'forward_algorithmic_tflops': round(r['forward_tflops'], 2),
         'roofline': r['roof'],
-        'scatter_aggregate': dict(r['scatter'], kernel='rg_segment_reduce_ordered sum over the step\'s '
-                                  'destination-major CSR, longest-first segment order (standalone; fused into the conv kernels in '
-                                  'the step)', bound='hbm', peak_gbs=HBM_PEAK_GBS),
         'kernels': r['kern'],
-        'clock': r['clock'],
     }
-    if args.config == 'm' and not args.no_extra:
+    if args.full:
+        line.update({
+            'forward_only_frames_per_s': round(r['forward_fps'], 2),
+            'forward_algorithmic_tflops': round(r['forward_tflops'], 2),
+            'scatter_aggregate': dict(r['scatter'], kernel='rg_segment_reduce_ordered sum over '
+                                      'the step\'s destination-major CSR, longest-first segment '
+                                      'order (standalone; fused into the conv kernels in the '
+                                      'step)', bound='hbm', peak_gbs=HBM_PEAK_GBS),
+            'clock': r['clock'],
+        })
+    if args.full and args.config == 'm' and not args.no_extra:
         # the same run also times BASELINE config 2 (bf16, random init) as an extra key
         a2 = argparse.Namespace(**vars(args))
         a2.config = 'c2'
+        a2.dump_outputs = None      # the dump holds the headline run's outputs
         for key, v in PRESETS['c2'].items():
             setattr(a2, key, v)
         cfg2 = default_config(graph_convolution_stem_channels=[64] * a2.layers,
@@ -1183,7 +1264,7 @@ def main():
                            'workload': workload_name(a2), 'edges_per_gpu': r2['E'],
                            'forward_only_frames_per_s': round(r2['forward_fps'], 2),
                            'roofline': r2['roof'], 'kernels': r2['kern'], 'clock': r2['clock']}
-    if rank == 0 and not args.no_cpu_baseline:  # after the timed region, every world size
+    if rank == 0 and args.full and not args.no_cpu_baseline:  # after the timed region
         log('cpu baseline')
         cb = cpu_baseline(args, cfg, sd)
         line['cpu_baseline'] = cb

@@ -32,6 +32,39 @@ def test_c5_overlaps_forwards(monkeypatch):
     assert pipeline.CONCURRENT_CONV_WAVES % 64 == 0   # rg_conv_layer_fused_waves' unit
 
 
+def test_plain_run_is_lean_and_full_is_an_option(monkeypatch):
+    a = _parse(monkeypatch)
+    assert a.full is False and a.dump_outputs is None
+    a = _parse(monkeypatch, '--full', '--dump-outputs', 'somewhere', '--steps', '7')
+    assert a.full is True and a.dump_outputs == 'somewhere' and a.steps == 7
+
+
+def test_dump_outputs_types_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs writes float32 / float64 .npy files (integers as float64); past the
+    byte budget every array keeps the same seeded share of its rows, the same rows each run."""
+    import numpy as np
+    import torch
+    arrays = {'a': torch.arange(12, dtype=torch.float32).reshape(6, 2).half(),
+              'idx': torch.arange(1000, dtype=torch.int32),
+              'd': np.linspace(0.0, 1.0, 5), 's': 3.5}
+    bench.dump_outputs(str(tmp_path / 'x'), 0, arrays)
+    got = {n: np.load(tmp_path / 'x' / f'{n}.npy') for n in arrays}
+    assert got['a'].dtype == np.float32 and got['a'].shape == (6, 2)
+    assert got['idx'].dtype == np.float64 and got['d'].dtype == np.float64
+    np.testing.assert_array_equal(got['idx'], np.arange(1000))
+    assert got['s'].shape == (1,) and got['s'][0] == 3.5
+    total = sum(v.nbytes for v in got.values())
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', total // 4)
+    for sub in ('y', 'z'):
+        bench.dump_outputs(str(tmp_path / sub), 1, arrays)
+    y = {n: np.load(tmp_path / 'y' / f'{n}.rank1.npy') for n in arrays}
+    z = {n: np.load(tmp_path / 'z' / f'{n}.rank1.npy') for n in arrays}
+    assert sum(v.nbytes for v in y.values()) <= total // 4 + 64
+    assert y['idx'].shape == (250,) and np.all(np.diff(y['idx']) > 0)
+    for n in arrays:
+        np.testing.assert_array_equal(y[n], z[n])
+
+
 @pytest.mark.parametrize('cfg', ['c2', 'c3', 'c5b'])
 def test_batched_16bit_presets_keep_build_overlap(monkeypatch, cfg):
     a = _parse(monkeypatch, '--config', cfg)

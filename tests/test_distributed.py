@@ -187,12 +187,12 @@ def _run_bench(args, timeout=240):
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_bench_gpus2_launches_two_ranks(cuda_device):
-    """`python bench.py --gpus 2` (no launcher in the environment) starts two ranks itself:
-    the line reports n_gpus 2 and the value counts both ranks' frames (weak scaling; gloo
-    for the timing collectives so both ranks can share the test box's one card), and rank 0
-    adds the CPU baseline after the timed region while the other rank waits."""
+    """`python bench.py --gpus 2 --full` (no launcher in the environment) starts two ranks
+    itself: the line reports n_gpus 2 and the value counts both ranks' frames (weak scaling;
+    gloo for the timing collectives so both ranks can share the test box's one card), and
+    rank 0 adds the CPU baseline (--full) after the timed region while the other rank waits."""
     line = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--frames', '4',
-                       '--nodes', '1000', '--cpu-frames', '1', '--no-extra'])
+                       '--nodes', '1000', '--cpu-frames', '1', '--no-extra', '--full'])
     assert line['n_gpus'] == 2
     # multi-rank lines carry the CPU baseline too (rank 0, after the timed region)
     cb = line['cpu_baseline']
@@ -222,7 +222,8 @@ def test_bench_c3_eight_ranks_512_frames(tmp_path, cuda_device):
     import bench
     world = 8
     line = _run_bench(['--config', 'c3', '--gpus', str(world), '--steps', '2', '--warmup', '1',
-                       '--cpu-frames', '1', '--save-outputs', str(tmp_path), '--save-frames', '2'],
+                       '--cpu-frames', '1', '--save-outputs', str(tmp_path), '--save-frames', '2',
+                       '--full'],
                       timeout=800)
     assert line['n_gpus'] == world
     assert line['config']['frames_per_rank_timed'] == [128] * world    # 64 frames x 2 steps
