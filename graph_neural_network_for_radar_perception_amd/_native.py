@@ -27,8 +27,10 @@ RG_PACK_CENTERED = 0x100
 RG_PACK_TRANSPOSE = 0x200
 RG_PACK_X3 = 0x400
 RG_PACK_F16 = 0x800
+RG_PACK_H2 = 0x1000
 RG_LAYER_CENTERED = 1
 RG_LAYER_F16 = 2
+RG_LAYER_H2 = 4
 RG_ERR_UNSUPPORTED = 3
 ACT = {'none': 0, 'relu': 1, 'leakyrelu': 2, 'swish': 3}
 GRAPH_KNN, GRAPH_RADIUS, GRAPH_KNN_RADIUS = 0, 1, 2
@@ -142,6 +144,7 @@ _SIGNATURES = {
                                  _P, _I, _I, _P, _P, _P, _I, _P, _I, _P]),
     'rg_mlp_chain_x3': (_I, [ctypes.POINTER(rg_layer), _I, _L, _P, _I, _P, _I, _I, _P, _P, _P,
                              _I, _P]),
+    'rg_h2_mfma_probe': (_I, [_P, _P, _P, _P]),
     'rg_conv_layer_f32_workspace_size': (_S, [_I]),
     'rg_conv_layer_f32': (_I, [ctypes.POINTER(rg_layer), _I, _P, _I, _P, _I, _P, _P, _P, _I, _P,
                                _I, _P, _S, _P]),

@@ -26,7 +26,11 @@ FLAGS = ['-O3', '-std=c++17', f'--offload-arch={ARCH}', '-fPIC', '-Wall',
 # per-source flags: the fused conv keeps its epilogue in scalar f32 (a packed v_pk_*_f32
 # beside MFMAs costs far more than two scalar ops, MI355X_MICROARCH.md "price of one
 # filler"); measured 3.5 % faster per conv layer than the packed build
-FILE_FLAGS = {'conv_fused.hip': ['-DRG_NO_PK', '-fno-slp-vectorize'],
+# chain_x3.hip: the h2 split's residues are two scalar fmas that read the halves of a packed
+# fp16 register (v_fma_mix_f32); the SLP vectoriser pairs them into a v_pk_fma_f32 behind two
+# unpacking conversions (5 instead of 4 VALU per pair, more registers, spills in two kernels)
+FILE_FLAGS = {'chain_x3.hip': ['-fno-slp-vectorize'],
+              'conv_fused.hip': ['-DRG_NO_PK', '-fno-slp-vectorize'],
               'conv_x3.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form']}
 
 

@@ -1,5 +1,7 @@
-// Register-resident FLOAT32 MLP chains on the bf16 matrix cores (x3_common.h: every
-// product from the exact three-term bf16 splits of both operands, f32 accumulation) for
+// Register-resident FLOAT32 MLP chains on the 16-bit matrix cores (x3_common.h: every
+// product from 16-bit splits of both operands, f32 accumulation, under the term scheme the
+// packed images carry -- h2, two fp16 terms and three products, RG_PACK_H2; or b3, three
+// exact bf16 terms and six products, RG_PACK_X3; every kernel below is a template of it) for
 // the widths of the shipped architecture: the fp32 path's node / edge encoders
 // (graph_feature_encoding, gnn_blocks.py:19-42) and the task-head chains
 // (gnn_blocks.py:167-389).  Same semantics as rg_mlp_chain_f32 (ffn_block chains: Linear
@@ -11,11 +13,15 @@
 //  * the encoders' un-normalised first layer (<= 8 inputs) is fused tile by tile into the
 //    second: each 32-feature output tile of layer 0 is activated, split and consumed at
 //    once as two k-steps of layer 1 (the 256-wide activation never exists in full);
-//  * packed weights (RG_PACK_X3) are staged in LDS per layer and plane where they fit
-//    (LMASK, 3 bits per layer); the rest is read from L2 through a buffer resource.  The
-//    7 -> 256 -> 128 -> 128 -> 64 edge encoder is 361 KiB of split weights: layer 0 and
-//    planes 0 / 1 of layer 1 (153 KiB) live in LDS, the others stream from L2, and two
-//    row tiles per wave halve that stream per flop.
+//  * packed weights are staged in LDS per layer and plane where they fit (LMASK, 3 bits
+//    per layer); the rest is read from L2 through a buffer resource.  The
+//    7 -> 256 -> 128 -> 128 -> 64 edge encoder is 361 KiB of split weights under b3: layer 0
+//    and planes 0 / 1 of layer 1 (153 KiB) live in LDS, the others stream from L2, and two
+//    row tiles per wave halve that stream per flop; under h2 it is 241 KiB, of which layer 0
+//    and both planes of layer 1 (144 KiB) live in LDS;
+//  * a scaled scheme's (h2) power-of-two weight scale is taken out once per layer: in the
+//    row scale of a normalised layer, in the activation of an un-normalised one, by one
+//    multiply at a plain output.
 #include "x3_common.h"
 
 namespace rg {
@@ -52,14 +58,14 @@ constexpr bool sp_act(int sp, int l) { return ((sp >> (8 + l)) & 1) != 0; }
 constexpr bool sp_cent(int sp) { return ((sp >> 16) & 1) != 0; }
 constexpr int lmask(int m, int l) { return (m >> (3 * l)) & 7; }
 
-template <int K0, int... Ns>
+template <typename P, int K0, int... Ns>
 struct Shape {
   static constexpr int NL = sizeof...(Ns);
   static constexpr int N[NL] = {Ns...};
   static constexpr int K(int l) { return l == 0 ? K0 : N[l - 1]; }
   static constexpr int pl(int l) { return plane_bytes(K(l), N[l]); }
-  static constexpr int bytes(int l) { return x3_bytes(K(l), N[l]); }
-  // LDS image: every layer's staged planes, then every layer's bias
+  static constexpr int bytes(int l) { return P::image_bytes(K(l), N[l]); }
+  // LDS image: every layer's staged planes, then every layer's bias (h2: and scale trailer)
   static constexpr int planes_lds(int LM, int l) {
     return (lmask(LM, l) & 1) + ((lmask(LM, l) >> 1) & 1) + ((lmask(LM, l) >> 2) & 1);
   }
@@ -70,7 +76,7 @@ struct Shape {
   }
   static constexpr int boff(int LM, int l) {
     int o = woff(LM, NL);
-    for (int i = 0; i < l; ++i) o += N[i] * 4;
+    for (int i = 0; i < l; ++i) o += P::tail_bytes(N[i]);
     return o;
   }
   static constexpr int lds_bytes(int LM) { return boff(LM, NL); }
@@ -100,15 +106,18 @@ struct Src {
   const char* lds;  // LDS base + lane * 16 of the layer's first staged plane
   int pl;
   WBuf g;
-  __device__ __forceinline__ bf16x8_t operator()(int plane, int off) const {
+  __device__ __forceinline__ u32x4 raw(int plane, int off) const {
     constexpr int m = lmask(LM, l);
     if ((m >> plane) & 1) {
       const int slot = plane == 0 ? 0 : (plane == 1 ? (m & 1) : (m & 1) + ((m >> 1) & 1));
-      return ld_bf8(lds + slot * pl + off);
+      return *(const u32x4*)(lds + slot * pl + off);
     }
-    return g(plane, off);
+    return g.raw(plane, off);
   }
 };
+
+// nrm: per layer {norm mu, norm std, descale 2^-s of a scaled scheme (else unused)}
+static constexpr int NR = 3;
 
 template <typename S, int LM, int l>
 __device__ __forceinline__ Src<LM, l> src_of(const Args& a, const char* lds, int lane) {
@@ -116,17 +125,17 @@ __device__ __forceinline__ Src<LM, l> src_of(const Args& a, const char* lds, int
                     wbuf(a.L[l].src, S::bytes(l), S::pl(l), lane)};
 }
 
-template <int SPEC, int l, int MT>
+template <typename P, int SPEC, int l, int MT>
 __device__ __forceinline__ void epilogue(f32x16 (&acc)[MT], const float* nrm) {
+  constexpr bool SC = P::SCALED;
   if constexpr (sp_norm(SPEC, l) && sp_act(SPEC, l)) {
-    norm_leaky<MT, sp_cent(SPEC)>(acc, nrm[2 * l], nrm[2 * l + 1]);
+    norm_leaky<MT, sp_cent(SPEC), SC>(acc, nrm[NR * l], nrm[NR * l + 1], nrm[NR * l + 2]);
   } else if constexpr (sp_norm(SPEC, l)) {
-    norm_only<MT, sp_cent(SPEC)>(acc, nrm[2 * l], nrm[2 * l + 1]);
-  } else if constexpr (sp_act(SPEC, l)) {
+    norm_only<MT, sp_cent(SPEC), SC>(acc, nrm[NR * l], nrm[NR * l + 1], nrm[NR * l + 2]);
+  } else if constexpr (SC || sp_act(SPEC, l)) {
+    const float ds = SC ? nrm[NR * l + 2] : 1.f;
 #pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[m][q] = act_t<ACT_LEAKY>(acc[m][q]);
+    for (int m = 0; m < MT; ++m) plain_epilogue<SC, sp_act(SPEC, l)>(acc[m], ds);
   }
 }
 
@@ -220,46 +229,39 @@ constexpr int pend_kind() {
   return !RG_X3_JIT ? 0 : (sp_norm(SPEC, l) && sp_act(SPEC, l)) ? 1 : sp_norm(SPEC, l) ? 2 : 0;
 }
 // layer l's epilogue when a next layer follows: statistics only for a pending kind
-template <int SPEC, int l, int MT, int RT>
+template <typename P, int SPEC, int l, int MT>
+__device__ __forceinline__ void epilogue_pend_one(f32x16 (&acc)[MT], const float* nrm, Pend& pn);
+template <typename P, int SPEC, int l, int MT, int RT>
 __device__ __forceinline__ void epilogue_pend(f32x16 (&acc)[RT][MT], const float* nrm,
                                               Pend (&pn)[RT]) {
-  constexpr int K = pend_kind<SPEC, l>();
 #pragma unroll
-  for (int t = 0; t < RT; ++t) {
-    if constexpr (K == 1) {
-      pn[t] = pend_norm_leaky<MT, sp_cent(SPEC)>(acc[t], nrm[2 * l], nrm[2 * l + 1]);
-    } else if constexpr (K == 2) {
-      pn[t] = pend_norm_only<MT, sp_cent(SPEC)>(acc[t], nrm[2 * l], nrm[2 * l + 1]);
-    } else {
-      epilogue<SPEC, l, MT>(acc[t], nrm);
-      pn[t] = Pend{0.f, 0.f};
-    }
-  }
+  for (int t = 0; t < RT; ++t) epilogue_pend_one<P, SPEC, l, MT>(acc[t], nrm, pn[t]);
 }
 
 // epilogue_pend of row tile t only
-template <int SPEC, int l, int MT>
+template <typename P, int SPEC, int l, int MT>
 __device__ __forceinline__ void epilogue_pend_one(f32x16 (&acc)[MT], const float* nrm, Pend& pn) {
   constexpr int K = pend_kind<SPEC, l>();
+  constexpr bool SC = P::SCALED;
   if constexpr (K == 1) {
-    pn = pend_norm_leaky<MT, sp_cent(SPEC)>(acc, nrm[2 * l], nrm[2 * l + 1]);
+    pn = pend_norm_leaky<MT, sp_cent(SPEC), SC>(acc, nrm[NR * l], nrm[NR * l + 1], nrm[NR * l + 2]);
   } else if constexpr (K == 2) {
-    pn = pend_norm_only<MT, sp_cent(SPEC)>(acc, nrm[2 * l], nrm[2 * l + 1]);
+    pn = pend_norm_only<MT, sp_cent(SPEC), SC>(acc, nrm[NR * l], nrm[NR * l + 1], nrm[NR * l + 2]);
   } else {
-    epilogue<SPEC, l, MT>(acc, nrm);
+    epilogue<P, SPEC, l, MT>(acc, nrm);
     pn = Pend{0.f, 0.f};
   }
 }
 // a layer's epilogue before the next layer: every row tile, or with RG_X3_SKEW at two row
 // tiles only tile 0 (tile 1's runs as the next layer_x3's pre1)
-template <int SPEC, int l, int MT, int RT>
+template <typename P, int SPEC, int l, int MT, int RT>
 __device__ __forceinline__ void epilogue_next(f32x16 (&acc)[RT][MT], const float* nrm,
                                               Pend (&pn)[RT]) {
   if constexpr (RG_X3_SKEW && RT == 2) {
-    epilogue_pend_one<SPEC, l, MT>(acc[0], nrm, pn[0]);
+    epilogue_pend_one<P, SPEC, l, MT>(acc[0], nrm, pn[0]);
     pn[1] = Pend{0.f, 0.f};
   } else {
-    epilogue_pend<SPEC, l, MT, RT>(acc, nrm, pn);
+    epilogue_pend<P, SPEC, l, MT, RT>(acc, nrm, pn);
   }
 }
 
@@ -268,8 +270,8 @@ __device__ __forceinline__ void epilogue_next(f32x16 (&acc)[RT][MT], const float
 // RG_X3_SKEW at RT = 2: row tile 1's epilogue of layer l - 1 not yet run at all)
 // pre: run after the last layer's MFMAs are issued, before its epilogue (the encoders' next-tile
 // input loads: the only loads then in flight, so no weight wait stalls behind them)
-template <typename S, int SPEC, int LM, int l, int RT, int PMT, int PEND, bool FULL = false,
-          typename Pre = NoHook>
+template <typename P, typename S, int SPEC, int LM, int l, int RT, int PMT, int PEND,
+          bool FULL = false, typename Pre = NoHook>
 __device__ __forceinline__ void run_rest(const Args& a, f32x16 (&prev)[RT][PMT], Pend (&pend)[RT],
                                          const char* lds, const float* nrm, long row0, long rows,
                                          int lane, Pre&& pre = Pre{}) {
@@ -282,30 +284,31 @@ __device__ __forceinline__ void run_rest(const Args& a, f32x16 (&prev)[RT][PMT],
   for (int t = 0; t < RT; ++t)
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[t][m] = ld_bias_frag(bias, m, h);
-  auto bop = [&](int s, int t) { return split_acc_pend<PEND>(prev[t][s >> 1], s & 1, pend[t]); };
+  auto bop = [&](int s, int t) { return split_acc_pend<PEND, P>(prev[t][s >> 1], s & 1, pend[t]); };
   if constexpr (RG_X3_SKEW && RT == 2) {
     layer_x3<KS, MT, MT, RT, x3_db<MT>()>(acc, src_of<S, LM, l>(a, lds, lane), 0, bop, [&]() {
-      epilogue_pend_one<SPEC, l - 1, PMT>(prev[1], nrm, pend[1]);
+      epilogue_pend_one<P, SPEC, l - 1, PMT>(prev[1], nrm, pend[1]);
     });
   } else {
     layer_x3<KS, MT, MT, RT, x3_db<MT>()>(acc, src_of<S, LM, l>(a, lds, lane), 0, bop);
   }
   if constexpr (l + 1 < S::NL) {
     Pend pn[RT];
-    epilogue_next<SPEC, l, MT, RT>(acc, nrm, pn);
-    run_rest<S, SPEC, LM, l + 1, RT, MT, pend_kind<SPEC, l>(), FULL>(a, acc, pn, lds, nrm, row0,
-                                                                    rows, lane, pre);
+    epilogue_next<P, SPEC, l, MT, RT>(acc, nrm, pn);
+    run_rest<P, S, SPEC, LM, l + 1, RT, MT, pend_kind<SPEC, l>(), FULL>(a, acc, pn, lds, nrm, row0,
+                                                                       rows, lane, pre);
   } else {
     pre();
 #pragma unroll
-    for (int t = 0; t < RT; ++t) epilogue<SPEC, l, MT>(acc[t], nrm);
+    for (int t = 0; t < RT; ++t) epilogue<P, SPEC, l, MT>(acc[t], nrm);
     store_rows<RT, MT, FULL>(acc, a, row0, rows, lane);
   }
 }
 
 // layer 0 over split inputs b0[t][s] (KS0 k-steps)
-template <typename S, int SPEC, int LM, int RT, int KS0>
-__device__ __forceinline__ void run_first(const Args& a, const X3 (&b0)[RT][KS0], const char* lds,
+template <typename P, typename S, int SPEC, int LM, int RT, int KS0>
+__device__ __forceinline__ void run_first(const Args& a, const typename P::terms (&b0)[RT][KS0],
+                                          const char* lds,
                                           const float* nrm, long row0, long rows, int lane) {
   constexpr int N = S::N[0], MT = N / 32;
   const int h = lane >> 5;
@@ -319,11 +322,11 @@ __device__ __forceinline__ void run_first(const Args& a, const X3 (&b0)[RT][KS0]
                                   [&](int s, int t) { return b0[t][s]; });
   if constexpr (S::NL > 1) {
     Pend pn[RT];
-    epilogue_next<SPEC, 0, MT, RT>(acc, nrm, pn);
-    run_rest<S, SPEC, LM, 1, RT, MT, pend_kind<SPEC, 0>()>(a, acc, pn, lds, nrm, row0, rows, lane);
+    epilogue_next<P, SPEC, 0, MT, RT>(acc, nrm, pn);
+    run_rest<P, S, SPEC, LM, 1, RT, MT, pend_kind<SPEC, 0>()>(a, acc, pn, lds, nrm, row0, rows, lane);
   } else {
 #pragma unroll
-    for (int t = 0; t < RT; ++t) epilogue<SPEC, 0, MT>(acc[t], nrm);
+    for (int t = 0; t < RT; ++t) epilogue<P, SPEC, 0, MT>(acc[t], nrm);
     store_rows<RT, MT>(acc, a, row0, rows, lane);
   }
 }
@@ -332,13 +335,16 @@ __device__ __forceinline__ void run_first(const Args& a, const X3 (&b0)[RT][KS0]
 // t = W0 x per NODE (rg_mlp_chain_x3 over the nodes, a bare last layer): the pair chain starts
 // from the gathered sum -- no layer-0 MFMAs and no split of the pair input (the link head's
 // pairs outnumber the nodes ~6x)
-template <typename S, int SPEC, int LM, int RT>
+template <typename P, typename S, int SPEC, int LM, int RT>
 __device__ __forceinline__ void run_pre(const Args& a, const char* lds, const float* nrm, long row0,
                                         long rows, int lane) {
   constexpr int N = S::N[0], MT = N / 32;
   static_assert(S::K(0) == N, "per-node rows t have layer 0's output width");
   const int r = lane & 31, h = lane >> 5;
   const float* bias = (const float*)(lds + S::boff(LM, 0));
+  // a scaled scheme stores b0 2^s: the rows t are true values, so the bias is descaled here
+  // (exact) and layer 0's norm runs unscaled (the kernel sets its nrm descale to 1)
+  const float ds0 = P::SCALED ? bias[N] : 1.f;
   f32x16 acc[RT][MT];
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
@@ -349,7 +355,8 @@ __device__ __forceinline__ void run_pre(const Args& a, const char* lds, const fl
     const float* pj = a.in0 + (size_t)j * a.ld0 + 4 * h;
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-      const f32x16 b = ld_bias_frag(bias, m, h);
+      f32x16 b = ld_bias_frag(bias, m, h);
+      if constexpr (P::SCALED) b *= ds0;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const f32x4 ti = *(const f32x4*)(pi + 32 * m + 8 * g);
@@ -361,14 +368,15 @@ __device__ __forceinline__ void run_pre(const Args& a, const char* lds, const fl
   }
   static_assert(S::NL > 1, "a pair chain continues after layer 0");
   Pend pn[RT];
-  epilogue_next<SPEC, 0, MT, RT>(acc, nrm, pn);
-  run_rest<S, SPEC, LM, 1, RT, MT, pend_kind<SPEC, 0>()>(a, acc, pn, lds, nrm, row0, rows, lane);
+  epilogue_next<P, SPEC, 0, MT, RT>(acc, nrm, pn);
+  run_rest<P, S, SPEC, LM, 1, RT, MT, pend_kind<SPEC, 0>()>(a, acc, pn, lds, nrm, row0, rows, lane);
 }
 
 // encoders: layer 0 (one k-step of <= 8 inputs, no normalisation) fused tile by tile into
 // layer 1: tile m0 of layer 0 is layer 1's k-steps 2 m0 and 2 m0 + 1
-template <typename S, int SPEC, int LM, int RT, typename Pre = NoHook>
-__device__ __forceinline__ void run_fused01(const Args& a, const X3 (&b0)[RT][1], const char* lds,
+template <typename P, typename S, int SPEC, int LM, int RT, typename Pre = NoHook>
+__device__ __forceinline__ void run_fused01(const Args& a, const typename P::terms (&b0)[RT][1],
+                                            const char* lds,
                                             const float* nrm, long row0, long rows, int lane,
                                             Pre&& pre = Pre{}) {
   constexpr int MT0 = S::N[0] / 32, MT1 = S::N[1] / 32, KS1 = S::N[0] / 16;
@@ -385,17 +393,18 @@ __device__ __forceinline__ void run_fused01(const Args& a, const X3 (&b0)[RT][1]
 #pragma unroll
     for (int m = 0; m < MT1; ++m) acc[t][m] = ld_bias_frag(bias1, m, h);
   // layer-1 A fragments of layer-0 tile m0 (k-steps 2 m0, 2 m0 + 1), read one tile ahead
-  auto lda1 = [&](int m0, bf16x8_t (&d)[2][MT1][3]) {
+  typedef typename P::vec vec;
+  auto lda1 = [&](int m0, vec (&d)[2][MT1][P::NP]) {
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
       for (int m = 0; m < MT1; ++m)
 #pragma unroll
-        for (int p = 0; p < 3; ++p) d[hf][m][p] = W1(p, (m * KS1 + 2 * m0 + hf) * 1024);
+        for (int p = 0; p < P::NP; ++p) d[hf][m][p] = P::cast(W1.raw(p, (m * KS1 + 2 * m0 + hf) * 1024));
   };
   // (measured: rolling this loop two tiles per iteration, 67 -> 47 KB of code, made the
   // edge encoder 12 % slower)
-  bf16x8_t A1[2][2][MT1][3];
+  vec A1[2][2][MT1][P::NP];
   lda1(0, A1[0]);
 #pragma unroll
   for (int m0 = 0; m0 < MT0; ++m0) {
@@ -405,32 +414,16 @@ __device__ __forceinline__ void run_fused01(const Args& a, const X3 (&b0)[RT][1]
 #pragma unroll
     for (int t = 0; t < RT; ++t) y[t][0] = ld_bias_frag(bias0, m0, h);
     layer_x3<1, 1, MT0, RT>(y, W0, m0, [&](int, int t) { return b0[t][0]; });
-    if constexpr (sp_act(SPEC, 0)) {
+    // (a scaled scheme: layer 0's descale, nrm[NR * 0 + 2], folded into its activation)
 #pragma unroll
-      for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) y[t][0][q] = act_t<ACT_LEAKY>(y[t][0][q]);
-    }
+    for (int t = 0; t < RT; ++t)
+      plain_epilogue<P::SCALED, sp_act(SPEC, 0)>(y[t][0], P::SCALED ? nrm[2] : 1.f);
     // layer-1 k-steps 2 m0, 2 m0 + 1 from this tile
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
-      const bf16x8_t(&A)[MT1][3] = A1[u][hf];
+      const vec(&A)[MT1][P::NP] = A1[u][hf];
 #pragma unroll
-      for (int t = 0; t < RT; ++t) {
-        const X3 b = split_acc(y[t][0], hf);
-#pragma unroll
-        for (int m = 0; m < MT1; ++m) acc[t][m] = mf(A[m][2], b.p0, acc[t][m]);
-#pragma unroll
-        for (int m = 0; m < MT1; ++m) acc[t][m] = mf(A[m][1], b.p1, acc[t][m]);
-#pragma unroll
-        for (int m = 0; m < MT1; ++m) acc[t][m] = mf(A[m][0], b.p2, acc[t][m]);
-#pragma unroll
-        for (int m = 0; m < MT1; ++m) acc[t][m] = mf(A[m][1], b.p0, acc[t][m]);
-#pragma unroll
-        for (int m = 0; m < MT1; ++m) acc[t][m] = mf(A[m][0], b.p1, acc[t][m]);
-#pragma unroll
-        for (int m = 0; m < MT1; ++m) acc[t][m] = mf(A[m][0], b.p0, acc[t][m]);
-      }
+      for (int t = 0; t < RT; ++t) products<P, MT1>(acc[t], A, split_acc_of<P>(y[t][0], hf));
     }
     // (the last tile unfenced, as layer_x3: layer 1's epilogue of row tile 0 may interleave
     // with tile 1's last MFMAs)
@@ -438,29 +431,34 @@ __device__ __forceinline__ void run_fused01(const Args& a, const X3 (&b0)[RT][1]
   }
   if constexpr (S::NL > 2) {
     Pend pn[RT];
-    epilogue_next<SPEC, 1, MT1, RT>(acc, nrm, pn);
-    run_rest<S, SPEC, LM, 2, RT, MT1, pend_kind<SPEC, 1>(), RG_X3_ENC_BUF>(a, acc, pn, lds, nrm, row0,
-                                                                         rows, lane, pre);
+    epilogue_next<P, SPEC, 1, MT1, RT>(acc, nrm, pn);
+    run_rest<P, S, SPEC, LM, 2, RT, MT1, pend_kind<SPEC, 1>(), RG_X3_ENC_BUF>(a, acc, pn, lds, nrm,
+                                                                            row0, rows, lane, pre);
   } else {
     pre();
 #pragma unroll
-    for (int t = 0; t < RT; ++t) epilogue<SPEC, 1, MT1>(acc[t], nrm);
+    for (int t = 0; t < RT; ++t) epilogue<P, SPEC, 1, MT1>(acc[t], nrm);
     store_rows<RT, MT1, RG_X3_ENC_BUF>(acc, a, row0, rows, lane);
   }
 }
 
-template <int MODE, int SPEC, int LM, int RT, int FT, int K0, int... Ns>
+template <typename P, int MODE, int SPEC, int LM, int RT, int FT, int K0, int... Ns>
 __global__ __launch_bounds__(FT) void chain_x3_kernel(Args a) {
-  using S = Shape<K0, Ns...>;
+  using S = Shape<P, K0, Ns...>;
+  typedef typename P::terms T;
   constexpr int NL = S::NL;
   constexpr int KS0 = (MODE == IN_SMALL || MODE == IN_PAIRPRE) ? 1 : K0 / 16;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  __shared__ float nrm[2 * RG_MAX_LAYERS];
+  __shared__ float nrm[NR * RG_MAX_LAYERS];
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
-      nrm[2 * l] = a.L[l].mu ? *a.L[l].mu : 0.f;
-      nrm[2 * l + 1] = a.L[l].sd ? *a.L[l].sd : 0.f;
+      nrm[NR * l] = a.L[l].mu ? *a.L[l].mu : 0.f;
+      nrm[NR * l + 1] = a.L[l].sd ? *a.L[l].sd : 0.f;
+      // (IN_PAIRPRE: layer 0's pre-activations arrive unscaled, run_pre)
+      nrm[NR * l + 2] = (P::SCALED && !(MODE == IN_PAIRPRE && l == 0))
+                            ? *(const float*)(a.L[l].src + P::NP * S::pl(l) + S::N[l] * 4)
+                            : 1.f;
     }
   }
   // stage the LDS planes and every bias (static layer indices: no scratch copy of a.L)
@@ -469,15 +467,15 @@ __global__ __launch_bounds__(FT) void chain_x3_kernel(Args a) {
     const int m = lmask(LM, l);
     int slot = 0;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
+    for (int p = 0; p < P::NP; ++p) {
       if ((m >> p) & 1) {
         stage_lds<FT>(lds + S::woff(LM, l) + slot * S::pl(l), a.L[l].src + p * S::pl(l), S::pl(l));
         ++slot;
       }
     }
-    const u32x4* bsrc = (const u32x4*)(a.L[l].src + 3 * S::pl(l));
+    const u32x4* bsrc = (const u32x4*)(a.L[l].src + P::NP * S::pl(l));
     u32x4* bdst = (u32x4*)(lds + S::boff(LM, l));
-    for (int i = threadIdx.x; i < S::N[l] / 4; i += FT) bdst[i] = bsrc[i];
+    for (int i = threadIdx.x; i < P::tail_bytes(S::N[l]) / 16; i += FT) bdst[i] = bsrc[i];
   }
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -514,9 +512,9 @@ __global__ __launch_bounds__(FT) void chain_x3_kernel(Args a) {
   for (long tile = (long)blockIdx.x * (FT / 64) + wave; tile < ntiles; tile += tstride) {
     const long row0 = tile * TROWS;
     if constexpr (MODE == IN_PAIRPRE) {
-      run_pre<S, SPEC, LM, RT>(a, lds, nrm, row0, rows, lane);
+      run_pre<P, S, SPEC, LM, RT>(a, lds, nrm, row0, rows, lane);
     } else {
-    X3 b0[RT][KS0];
+    T b0[RT][KS0];
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
       const long row = row0 + 32 * t + r;
@@ -532,12 +530,12 @@ __global__ __launch_bounds__(FT) void chain_x3_kernel(Args a) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = (ok && h == 0 && j < a.w0real) ? p[j] : 0.f;
         }
-        b0[t][0] = split8((f32x4){v[0], v[1], v[2], v[3]}, (f32x4){v[4], v[5], v[6], v[7]});
+        b0[t][0] = P::split((f32x4){v[0], v[1], v[2], v[3]}, (f32x4){v[4], v[5], v[6], v[7]});
       } else if constexpr (MODE == IN_DENSE) {
         const float* p = a.in0 + (size_t)(ok ? row : 0) * a.ld0 + 8 * h;
 #pragma unroll
         for (int s = 0; s < KS0; ++s)
-          b0[t][s] = split8(*(const f32x4*)(p + 16 * s), *(const f32x4*)(p + 16 * s + 4));
+          b0[t][s] = P::split(*(const f32x4*)(p + 16 * s), *(const f32x4*)(p + 16 * s + 4));
       } else {
         const int i = ok ? a.idx0[row] : 0, j = ok ? a.idx1[row] : 0;
         const float* pi = a.in0 + (size_t)i * a.ld0 + 8 * h;
@@ -552,28 +550,28 @@ __global__ __launch_bounds__(FT) void chain_x3_kernel(Args a) {
             u[k] = (f32x4){__fadd_rn(xi.x, xj.x), __fadd_rn(xi.y, xj.y), __fadd_rn(xi.z, xj.z),
                            __fadd_rn(xi.w, xj.w)};
           }
-          b0[t][s] = split8(u[0], u[1]);
+          b0[t][s] = P::split(u[0], u[1]);
         }
       }
     }
     if constexpr (MODE == IN_SMALL && RG_X3_INPF)
-      run_fused01<S, SPEC, LM, RT>(a, b0, lds, nrm, row0, rows, lane, [&]() {
+      run_fused01<P, S, SPEC, LM, RT>(a, b0, lds, nrm, row0, rows, lane, [&]() {
         if (tile + tstride < ntiles) load_in(tile + tstride);
       });
     else if constexpr (MODE == IN_SMALL)
-      run_fused01<S, SPEC, LM, RT>(a, b0, lds, nrm, row0, rows, lane);
+      run_fused01<P, S, SPEC, LM, RT>(a, b0, lds, nrm, row0, rows, lane);
     else
-      run_first<S, SPEC, LM, RT, KS0>(a, b0, lds, nrm, row0, rows, lane);
+      run_first<P, S, SPEC, LM, RT, KS0>(a, b0, lds, nrm, row0, rows, lane);
     }
   }
 }
 
-template <int MODE, int SPEC, int LM, int RT, int FT, int K0, int... Ns>
+template <typename P, int MODE, int SPEC, int LM, int RT, int FT, int K0, int... Ns>
 static int launch(const Args& a, hipStream_t st) {
-  using S = Shape<K0, Ns...>;
+  using S = Shape<P, K0, Ns...>;
   constexpr int lds = S::lds_bytes(LM);
   static_assert(lds <= DYN_LDS_MAX, "chain_x3: LDS image too large");
-  auto kern = chain_x3_kernel<MODE, SPEC, LM, RT, FT, K0, Ns...>;
+  auto kern = chain_x3_kernel<P, MODE, SPEC, LM, RT, FT, K0, Ns...>;
   RG_ENSURE_LDS(kern, lds);
   const long tiles = (a.rows + 32 * RT - 1) / (32 * RT);
   long blocks = (tiles + FT / 64 - 1) / (FT / 64);
@@ -617,20 +615,24 @@ static bool match(const Key& k, int mode, int k0, int sp, std::initializer_list<
 #define RG_X3_HEAD_RT 1  // row tiles per wave of the 5-layer task-head chains (two waves / SIMD at 1)
 #endif
 
+template <typename P>
 static int dispatch(const Key& k, const Args& a, hipStream_t st) {
 #define RG_X3C(MODE, K0, SP, LM, RT, FT, ...) \
-  if (match(k, MODE, K0, SP, {__VA_ARGS__})) return launch<MODE, SP, LM, RT, FT, K0, __VA_ARGS__>(a, st);
-  constexpr int ALL = 07777777;  // every plane of every layer in LDS
+  if (match(k, MODE, K0, SP, {__VA_ARGS__})) return launch<P, MODE, SP, LM, RT, FT, K0, __VA_ARGS__>(a, st);
+  constexpr int ALL = P::NP == 3 ? 07777777 : 03333333;  // every plane of every layer in LDS
+  // the encoders' LDS residency: b3 layer 0 + planes 0, 1 of layer 1 (153 KiB of the edge
+  // encoder's 361 KiB); h2 layer 0 + both planes of layer 1 (144 KiB of 241 KiB: the next
+  // largest plane, 16 KiB of the last layer, no longer fits beside the biases)
+  constexpr int ENC = P::NP == 3 ? (07 | (03 << 3)) : (03 | (03 << 3));
   constexpr int EFT = RG_X3_ENC_FT ? RG_X3_ENC_FT : (RG_X3_ENC_RT >= 2 ? 256 : 512);
-  // edge encoder 7 -> 256 -> 128 -> 128 -> 64 (gnn_blocks.py:19-42, block 0 without norm):
-  // LDS = layer 0 + planes 0, 1 of layer 1
+  // edge encoder 7 -> 256 -> 128 -> 128 -> 64 (gnn_blocks.py:19-42, block 0 without norm)
   // (each shape twice: normalised layers packed centred -- the engine's choice -- or not)
 #define RG_X3C2(MODE, K0, NM, AM, LM, RT, FT, ...)                      \
   RG_X3C(MODE, K0, spec(NM, AM, true), LM, RT, FT, __VA_ARGS__)         \
   RG_X3C(MODE, K0, spec(NM, AM, false), LM, RT, FT, __VA_ARGS__)
-  RG_X3C2(IN_SMALL, 7, 0b1110, 0b1111, 07 | (03 << 3), RG_X3_ENC_RT, EFT, 256, 128, 128, 64)
+  RG_X3C2(IN_SMALL, 7, 0b1110, 0b1111, ENC, RG_X3_ENC_RT, EFT, 256, 128, 128, 64)
   // node encoder 6 -> 256 -> 128 -> 64
-  RG_X3C2(IN_SMALL, 6, 0b110, 0b111, 07 | (03 << 3), RG_X3_ENC_RT, EFT, 256, 128, 64)
+  RG_X3C2(IN_SMALL, 6, 0b110, 0b111, ENC, RG_X3_ENC_RT, EFT, 256, 128, 64)
   // task heads: 3-block stem + FFN_TaskSpecificHead (ffn + bare Linear -> 7 / 2, padded)
   constexpr int HFT = RG_X3_HEAD_RT == 1 ? RG_X3_HEAD_FT : 256;
   RG_X3C2(IN_DENSE, 64, 0b1111, 0b1111, ALL, RG_X3_HEAD_RT, HFT, 64, 64, 64, 64, 32)
@@ -656,6 +658,30 @@ static int dispatch(const Key& k, const Args& a, hipStream_t st) {
 
 using namespace rg;
 using namespace rg::cx3;
+
+// one 32x32x16 f16 MFMA with the operand and accumulator layouts of the h2 kernels
+__global__ __launch_bounds__(64) void h2_probe_kernel(const uint16_t* __restrict__ A,
+                                                      const uint16_t* __restrict__ B,
+                                                      float* __restrict__ C) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const f16x8_t a = H2P::cast(*(const u32x4*)(A + r * 16 + 8 * h));
+  const f16x8_t b = H2P::cast(*(const u32x4*)(B + r * 16 + 8 * h));
+  f32x16 c;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) c[q] = 0.f;
+  c = H2P::mfma(a, b, c);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) C[(8 * (q >> 2) + 4 * h + (q & 3)) * 32 + r] = c[q];
+}
+
+extern "C" int rg_h2_mfma_probe(const uint16_t* a, const uint16_t* b, float* c, void* stream) {
+  RG_REQUIRE(a && b && c, RG_ERR_ARG, "rg_h2_mfma_probe: null argument");
+  RG_REQUIRE(((uintptr_t)a | (uintptr_t)b) % 16 == 0, RG_ERR_ARG,
+             "rg_h2_mfma_probe: operands must be 16-byte aligned");
+  h2_probe_kernel<<<1, 64, 0, (hipStream_t)stream>>>(a, b, c);
+  RG_LAUNCH_CHECK();
+  return RG_OK;
+}
 
 static int chain_x3(const rg_layer* layers, int n_layers, long rows, const int* rows_dev,
                     int in_mode, const float* in0, int ld0, int w0, const int* idx0,
@@ -728,10 +754,15 @@ static int chain_x3(const rg_layer* layers, int n_layers, long rows, const int* 
   a.out = out;
   a.ld_out = ld_out;
   a.out_real = layers[n_layers - 1].out_dim;
+  // the term scheme of the packed images: RG_PACK_H2 on every layer, or on none
+  int h2 = 0;
+  for (int l = 0; l < n_layers; ++l) h2 += (layers[l].flags & RG_LAYER_H2) ? 1 : 0;
+  RG_REQUIRE(h2 == 0 || h2 == n_layers, RG_ERR_ARG,
+             "rg_mlp_chain_x3: RG_LAYER_H2 on every layer of a chain or on none");
   if (rows <= 0) return RG_OK;
   // encoders' buffer stores (RG_X3_ENC_BUF): full-width 16-B aligned rows, 32-bit byte offsets
   if (RG_X3_ENC_BUF && k.mode == IN_SMALL &&
       (a.out_real != k.n[n_layers - 1] || ld_out % 4 != 0 || (double)rows * ld_out * 4 > 0x7ff00000))
     return RG_ERR_UNSUPPORTED;
-  return dispatch(k, a, (hipStream_t)stream);
+  return h2 ? dispatch<H2P>(k, a, (hipStream_t)stream) : dispatch<B3>(k, a, (hipStream_t)stream);
 }

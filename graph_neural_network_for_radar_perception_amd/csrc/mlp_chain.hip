@@ -57,6 +57,9 @@ __host__ __device__ inline size_t frag_bytes(int in_dim, int out_dim, int dtype)
   return mt * (kpad(in_dim, 32) / 32) * 64 * 8 * sizeof(uint16_t);
 }
 static size_t packed_bytes(int in_dim, int out_dim, int dtype) {
+  if (dtype & RG_PACK_H2)  // two fp16 planes, the scaled bias (accumulator order), the scale
+    return 2 * frag_bytes(in_dim, out_dim, dtype & ~RG_PACK_H2) +
+           (size_t)kpad(out_dim, 32) * sizeof(float) + 16;
   if (dtype & RG_PACK_X3)  // three bf16 planes, then the bias (accumulator order)
     return 3 * frag_bytes(in_dim, out_dim, dtype & ~RG_PACK_X3) + (size_t)kpad(out_dim, 32) * sizeof(float);
   const int bpad = (dtype == RG_PACK_FAST_IN || dtype == RG_PACK_FAST_CHAIN ||
@@ -151,11 +154,9 @@ __global__ void pack_bf16_kernel(const float* __restrict__ W, int in, int out, i
 // plane p > 0 (RG_PACK_X3): the p-th bf16 term of the exact three-term split of each
 // weight, w = bf16(w) + bf16(w - w0) + bf16(w - w0 - w1) (conv_x3.hip)
 // f16 (RG_PACK_F16): IEEE fp16 fragments instead of bf16
-__global__ void pack_fast_kernel(const float* __restrict__ W, int in, int out, int mem_steps,
-                                 int center, int plane, int f16, uint16_t* __restrict__ P,
-                                 long total) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
+// element t of a fast-format plane: the (centred) weight it holds, 0 in the padding
+__device__ inline float fast_elem(const float* __restrict__ W, int in, int out, int mem_steps,
+                                  int center, long t) {
   const int S = (in + 15) / 16;
   const int j = (int)(t & 7);
   const int lane = (int)((t >> 3) & 63);
@@ -177,8 +178,65 @@ __global__ void pack_fast_kernel(const float* __restrict__ W, int in, int out, i
       v -= cs / (float)out;
     }
   }
+  return v;
+}
+__global__ void pack_fast_kernel(const float* __restrict__ W, int in, int out, int mem_steps,
+                                 int center, int plane, int f16, uint16_t* __restrict__ P,
+                                 long total) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  float v = fast_elem(W, in, out, mem_steps, center, t);
   for (int q = 0; q < plane; ++q) v -= bf16_to_f32(f32_to_bf16(v));  // exact residues
   P[t] = f16 ? f32_to_f16(v) : f32_to_bf16(v);
+}
+
+// RG_PACK_H2: the layer's power-of-two scale from max |w| (centred as the planes are), one
+// workgroup; tr = {2^-s, 2^s, (int) s, 0} with max |w| 2^s in [2^12, 2^13), |s| <= 64
+static constexpr int H2_SMAX = 64;
+__global__ void h2_scale_kernel(const float* __restrict__ W, int in, int out, int center,
+                                float* __restrict__ tr) {
+  __shared__ float red[256];
+  float mx = 0.f;
+  for (int k = threadIdx.x; k < in; k += 256) {
+    float mean = 0.f;
+    if (center) {  // the same sum, in the same order, as fast_elem's
+      float cs = 0.f;
+      for (int oo = 0; oo < out; ++oo) cs += W[(size_t)oo * in + k];
+      mean = cs / (float)out;
+    }
+    for (int o = 0; o < out; ++o) {
+      const float v = center ? W[(size_t)o * in + k] - mean : W[(size_t)o * in + k];
+      mx = fmaxf(mx, fabsf(v));
+    }
+  }
+  red[threadIdx.x] = mx;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    int s = 0;
+    if (red[0] > 0.f && red[0] < INFINITY) {
+      int e;
+      frexpf(red[0], &e);  // max = m 2^e, m in [0.5, 1): max 2^(13 - e) in [2^12, 2^13)
+      s = min(max(13 - e, -H2_SMAX), H2_SMAX);
+    }
+    tr[0] = ldexpf(1.f, -s);
+    tr[1] = ldexpf(1.f, s);
+    ((int*)tr)[2] = s;
+    tr[3] = 0.f;
+  }
+}
+// plane 0: fp16(w 2^s), plane 1: fp16(w 2^s - plane 0) (the residue exact in f32)
+__global__ void pack_fast_h2_kernel(const float* __restrict__ W, int in, int out, int mem_steps,
+                                    int center, int plane, const float* __restrict__ tr,
+                                    uint16_t* __restrict__ P, long total) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  float v = fast_elem(W, in, out, mem_steps, center, t) * tr[1];
+  if (plane) v -= f16_to_f32(f32_to_f16(v));
+  P[t] = f32_to_f16(v);
 }
 
 // RG_PACK_F32_FAST: [m][s4][lane][4] = W[32m + (lane&31)][8 s4 + 4 (lane>>5) + u]; the k
@@ -211,8 +269,9 @@ __global__ void pack_bias_kernel(const float* __restrict__ b, int out, int n, fl
 // fast formats: the bias in 32x32 accumulator order, [m][h][16] with entry
 // 4g + j = bias[32m + 8g + 4h + j], so lane half h of M-tile m initialises its 16
 // accumulators with four contiguous 16-B LDS reads (no register moves)
+// tr (RG_PACK_H2): the layer's scale trailer; the bias is stored times 2^s (exact)
 __global__ void pack_bias_frag_kernel(const float* __restrict__ b, int out, int n, int center,
-                                      float* __restrict__ P) {
+                                      float* __restrict__ P, const float* __restrict__ tr = nullptr) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   const int m = t >> 5, h = (t >> 4) & 1, g = (t >> 2) & 3, j = t & 3;
@@ -223,7 +282,7 @@ __global__ void pack_bias_frag_kernel(const float* __restrict__ b, int out, int 
     for (int o = 0; o < out; ++o) cs += b[o];
     v -= cs / (float)out;
   }
-  P[t] = v;
+  P[t] = tr ? v * tr[1] : v;
 }
 
 // ------------------------------------------------------------------ element access
@@ -650,6 +709,28 @@ extern "C" size_t rg_packed_linear_bytes(int in_dim, int out_dim, int dtype) {
   return packed_bytes(in_dim, out_dim, dtype & ~(RG_PACK_CENTERED | RG_PACK_TRANSPOSE | RG_PACK_F16));
 }
 
+// RG_PACK_H2: two scaled fp16 planes of one RG_PACK_FAST_IN / _CHAIN format, the scaled bias,
+// the scale
+static int pack_h2(const float* weight, const float* bias, int in_dim, int out_dim, int fmt,
+                   int center, void* packed, hipStream_t st) {
+  RG_REQUIRE(fmt == RG_PACK_FAST_IN || fmt == RG_PACK_FAST_CHAIN, RG_ERR_ARG,
+             "rg_pack_linear: RG_PACK_H2 applies to RG_PACK_FAST_IN and RG_PACK_FAST_CHAIN");
+  const int ks = (in_dim + 15) / 16;
+  const int mem_steps = fmt == RG_PACK_FAST_IN ? ks : 0;
+  const size_t fb = frag_bytes(in_dim, out_dim, fmt);
+  const long total = (long)fb / sizeof(uint16_t);
+  const int nb = kpad(out_dim, 32);
+  float* pb = (float*)((char*)packed + 2 * fb);
+  float* tr = pb + nb;
+  h2_scale_kernel<<<1, 256, 0, st>>>(weight, in_dim, out_dim, center, tr);
+  for (int p = 0; p < 2; ++p)
+    pack_fast_h2_kernel<<<ceil_div(total, 256), 256, 0, st>>>(
+        weight, in_dim, out_dim, mem_steps, center, p, tr, (uint16_t*)((char*)packed + p * fb), total);
+  pack_bias_frag_kernel<<<ceil_div(nb, 256), 256, 0, st>>>(bias, out_dim, nb, center, pb, tr);
+  RG_LAUNCH_CHECK();
+  return RG_OK;
+}
+
 // RG_PACK_X3: three planes of one RG_PACK_FAST_* format, or of RG_BF16 (the generic chain's
 // 16x16x32 fragments; transpose allowed), then the f32 bias
 static int pack_x3(const float* weight, const float* bias, int in_dim, int out_dim, int fmt,
@@ -698,6 +779,12 @@ extern "C" int rg_pack_linear(const float* weight, const float* bias, int in_dim
   RG_REQUIRE(!f16 || dtype == RG_BF16 || ((dtype & ~RG_PACK_CENTERED) >= RG_PACK_FAST_IN &&
                                           (dtype & ~RG_PACK_CENTERED) <= RG_PACK_FAST_UPD),
              RG_ERR_ARG, "rg_pack_linear: RG_PACK_F16 applies to RG_BF16 and the RG_PACK_FAST_* formats");
+  if (dtype & RG_PACK_H2) {
+    RG_REQUIRE(!f16 && !(dtype & (RG_PACK_X3 | RG_PACK_TRANSPOSE)), RG_ERR_ARG,
+               "rg_pack_linear: RG_PACK_H2 excludes RG_PACK_X3, RG_PACK_F16 and RG_PACK_TRANSPOSE");
+    return pack_h2(weight, bias, in_dim, out_dim, dtype & ~(RG_PACK_H2 | RG_PACK_CENTERED),
+                   (dtype & RG_PACK_CENTERED) ? 1 : 0, packed, st);
+  }
   if (dtype & RG_PACK_X3) {
     return pack_x3(weight, bias, in_dim, out_dim,
                    dtype & ~(RG_PACK_X3 | RG_PACK_CENTERED | RG_PACK_TRANSPOSE),

@@ -51,6 +51,26 @@ def _half_flag(dtype: str) -> int:
 # (rg_conv_layer_f32).  Both keep float32 accuracy (tests/test_gpu_f32.py runs both by
 # setting this attribute; nothing reads the environment).
 F32_ARITH = 'x3'
+# Term scheme of the 'x3' MLP chains (encoders, task heads; rg_mlp_chain_x3): 'h2' = two-term
+# IEEE fp16 splits, three MFMA products per f32 product (RG_PACK_H2: half the matrix work,
+# float32-class results, every converted value |a| < 2**15 -- an overflow comes back
+# non-finite); 'b3' = exact three-term bf16 splits, six products (RG_PACK_X3: no range
+# limit).  The fused conv layers run 'b3' either way.  Read when a chain is first packed or
+# called after a change.
+X3_TERMS = 'h2'
+H2_MAX_ABS = 2.0 ** 15   # the 'h2' domain: every value a chain converts to fp16 is below this
+
+
+def h2_scale_exp(max_abs: float) -> int:
+    """The exponent s of an RG_PACK_H2 layer's power-of-two weight scale, as rg_pack_linear
+    chooses it from the layer's largest |w| (after centring): max_abs * 2**s lies in
+    [2**12, 2**13), clamped to |s| <= 64; 0 for an all-zero (or non-finite) layer.  The packed
+    image stores s itself; this mirror serves callers that reason about the scale on the host."""
+    import math
+    if not (max_abs > 0.0 and math.isfinite(max_abs)):
+        return 0
+    _, e = math.frexp(max_abs)   # max_abs = m 2**e, m in [0.5, 1)
+    return min(max(13 - e, -64), 64)
 # fp32 link head with its first Linear per node (ModelPlans.link_pairs_pre); False = per pair
 LINK_PRE = True
 # x3 conv over the per-graph work-block table (rg_conv_x3_blocks: LPT order, 8-node tail);
@@ -166,7 +186,8 @@ def layer_array(specs: List[LayerSpec], base: int, offs: List[int], fmts=None):
     for i, s in enumerate(specs):
         arr[i].flags = ((nat.RG_LAYER_CENTERED
                          if fmts is not None and fmts[i] & nat.RG_PACK_CENTERED else 0)
-                        | (nat.RG_LAYER_F16 if fmts is not None and fmts[i] & nat.RG_PACK_F16 else 0))
+                        | (nat.RG_LAYER_F16 if fmts is not None and fmts[i] & nat.RG_PACK_F16 else 0)
+                        | (nat.RG_LAYER_H2 if fmts is not None and fmts[i] & nat.RG_PACK_H2 else 0))
         arr[i].w_packed = base + offs[i]
         arr[i].norm_mu = nat.ptr(s.mu.detach()) if s.mu is not None else None
         arr[i].norm_std = nat.ptr(s.std.detach()) if s.std is not None else None
@@ -322,8 +343,11 @@ class ChainPlan:
     def _x3_layers(self):
         """The chain packed RG_PACK_X3 (layer 0 FAST_IN, later FAST_CHAIN) for
         rg_mlp_chain_x3 (lazily)."""
-        if self._x3 is None:
-            X3 = nat.RG_PACK_X3
+        if self._x3 is None or self._x3_terms != X3_TERMS:
+            if X3_TERMS not in ('h2', 'b3'):
+                raise ValueError(f"engine.X3_TERMS must be 'h2' or 'b3', not {X3_TERMS!r}")
+            X3 = nat.RG_PACK_H2 if X3_TERMS == 'h2' else nat.RG_PACK_X3
+            self._x3_terms = X3_TERMS
             self._x3buf, groups = self._pack_buffer(lambda i: centered_fmt(
                 self.specs[i], (nat.RG_PACK_FAST_IN if i == 0 else nat.RG_PACK_FAST_CHAIN) | X3))
             self._x3 = groups[0][0]

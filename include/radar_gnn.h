@@ -73,6 +73,16 @@ extern "C" {
 /* OR-ed into a RG_PACK_FAST_* format: IEEE fp16 fragments instead of bf16 (round to nearest
  * even); mark such layers RG_LAYER_F16 -- the 16-bit kernels then take fp16 operands */
 #define RG_PACK_F16 0x800
+/* OR-ed into a RG_PACK_FAST_* format (with RG_PACK_CENTERED as RG_PACK_X3 takes it): the
+ * two-term IEEE fp16 split of every weight times a power of two 2^s per layer,
+ * w 2^s = w0 + w1 + r (w0 = fp16(w 2^s), w1 = fp16(w 2^s - w0), |r| <= 2^-21 |w| 2^s + 2^-25),
+ * as two planes of that format back to back, then the float32 bias times 2^s in accumulator
+ * order, then 16 bytes {float 2^-s, float 2^s, int s, 0}.  s is chosen so that the largest
+ * |w| of the layer (after centring) times 2^s lies in [2^12, 2^13), within |s| <= 64 (s = 0
+ * for an all-zero layer).  The operand format of rg_mlp_chain_x3's three-product scheme: mark
+ * such layers RG_LAYER_H2.  Every activation such a chain converts must be below 2^15 in
+ * magnitude (fp16 overflows above 65504; the row then comes back non-finite). */
+#define RG_PACK_H2 0x1000
 
 /* activations (modules/neural_net/common.py:256-267) */
 #define RG_ACT_NONE 0
@@ -284,6 +294,8 @@ typedef struct rg_layer {
 #define RG_LAYER_CENTERED 1 /* w_packed was packed with RG_PACK_CENTERED */
 #define RG_LAYER_F16 2      /* w_packed holds fp16 fragments (RG_PACK_F16): the fast chain /
                                fused conv then read and write RG_F16 activations */
+#define RG_LAYER_H2 4       /* w_packed was packed with RG_PACK_H2 (rg_mlp_chain_x3: every layer
+                               of a chain, or none) */
 
 #define RG_MAX_LAYERS 8
 
@@ -346,8 +358,11 @@ int rg_mlp_chain_f32_ex(const rg_layer* layers_host, int n_layers, long rows, co
 /* The same float32 chains on the bf16 matrix cores: every product formed from the exact
  * three-term bf16 splits of both operands (RG_PACK_X3, see rg_conv_layer_x3), f32
  * accumulation -- float32 accuracy at 2.7x the f32 MFMA rate.  Layer 0 packed
- * RG_PACK_FAST_IN | RG_PACK_X3, later layers RG_PACK_FAST_CHAIN | RG_PACK_X3, no
- * RG_LAYER_CENTERED; in_mode and the rest as rg_mlp_chain_f32 (dense inputs of <= 8 features
+ * RG_PACK_FAST_IN | RG_PACK_X3, later layers RG_PACK_FAST_CHAIN | RG_PACK_X3.  With
+ * RG_PACK_H2 in place of RG_PACK_X3 on every layer (RG_LAYER_H2), each product is formed from
+ * two-term fp16 splits in three MFMAs instead of six: float32-class results (the dropped
+ * terms are below 2^-21 of a product, under the f32 accumulation error), half the matrix
+ * work, inputs and activations limited to |a| < 2^15.  in_mode and the rest as rg_mlp_chain_f32 (dense inputs of <= 8 features
  * with an un-normalised first layer, or widths that are multiples of 16).  Returns
  * RG_ERR_UNSUPPORTED (launching nothing) for shapes without an instantiation, and for the
  * <= 8-input (encoder) shapes also unless the output rows are full width (last out_dim a
@@ -356,6 +371,12 @@ int rg_mlp_chain_f32_ex(const rg_layer* layers_host, int n_layers, long rows, co
 int rg_mlp_chain_x3(const rg_layer* layers_host, int n_layers, long rows, const int* rows_dev,
                     int in_mode, const float* in0, int ld0, int w0, const int* idx0,
                     const int* idx1, float* out, int ld_out, void* stream);
+
+/* One v_mfma_f32_32x32x16_f16 as the RG_PACK_H2 kernels issue it (one wave, zero
+ * accumulators): c[m][n] = sum_k a[m][k] b[n][k] with a, b fp16 bit patterns, row-major
+ * [32][16], and c float32 [32][32].  The h2 arithmetic rests on fp16 SUBNORMAL operands
+ * being honoured, not flushed; the test suite pins that with this entry. */
+int rg_h2_mfma_probe(const uint16_t* a, const uint16_t* b, float* c, void* stream);
 
 /* One fused FLOAT32 residual_graph_conv_block (gnn_blocks.py:96-113, the reference
  * precision) for the shipped widths (C = 64, message MLP 192 -> 128 -> 64, update
