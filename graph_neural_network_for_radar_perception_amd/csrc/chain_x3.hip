@@ -265,6 +265,30 @@ __device__ __forceinline__ void epilogue_next(f32x16 (&acc)[RT][MT], const float
   }
 }
 
+// An un-normalised OUTPUT layer adds its bias after its products, not before: accumulators that
+// start from the bias take one rounding at the bias's magnitude per MFMA pass, and a
+// classification head's prior bias (-log 99) is ~100 x its W x -- 5 x (rms) and 11 x (max) the
+// error of a float32 evaluation, against 1 x with the single rounding of the final add
+// (tests/test_gpu_chain_x3.py::test_f32_class_error).  A normalised layer's bias is of the size
+// of its products and is divided by the row's deviation: it stays the accumulators' start.
+template <typename S, int SPEC, int l>
+constexpr bool bias_last() {
+  return l + 1 == S::NL && !sp_norm(SPEC, l);
+}
+__device__ __forceinline__ f32x16 zero16() {
+  f32x16 z;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) z[q] = 0.f;
+  return z;
+}
+template <int RT, int MT>
+__device__ __forceinline__ void add_bias(f32x16 (&acc)[RT][MT], const float* bias, int h) {
+#pragma unroll
+  for (int t = 0; t < RT; ++t)
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[t][m] += ld_bias_frag(bias, m, h);
+}
+
 // layers l.. of the chain; prev = the previous layer's activations (RT row tiles), with
 // the previous layer's norm / act still pending (PEND) where pend_kind says so (with
 // RG_X3_SKEW at RT = 2: row tile 1's epilogue of layer l - 1 not yet run at all)
@@ -279,11 +303,12 @@ __device__ __forceinline__ void run_rest(const Args& a, f32x16 (&prev)[RT][PMT],
   static_assert(S::K(l) == 32 * PMT, "chained width");
   const int h = lane >> 5;
   const float* bias = (const float*)(lds + S::boff(LM, l));
+  constexpr bool BL = bias_last<S, SPEC, l>();
   f32x16 acc[RT][MT];
 #pragma unroll
   for (int t = 0; t < RT; ++t)
 #pragma unroll
-    for (int m = 0; m < MT; ++m) acc[t][m] = ld_bias_frag(bias, m, h);
+    for (int m = 0; m < MT; ++m) acc[t][m] = BL ? zero16() : ld_bias_frag(bias, m, h);
   auto bop = [&](int s, int t) { return split_acc_pend<PEND, P>(prev[t][s >> 1], s & 1, pend[t]); };
   if constexpr (RG_X3_SKEW && RT == 2) {
     layer_x3<KS, MT, MT, RT, x3_db<MT>()>(acc, src_of<S, LM, l>(a, lds, lane), 0, bop, [&]() {
@@ -299,6 +324,7 @@ __device__ __forceinline__ void run_rest(const Args& a, f32x16 (&prev)[RT][PMT],
                                                                        rows, lane, pre);
   } else {
     pre();
+    if constexpr (BL) add_bias<RT, MT>(acc, bias, h);
 #pragma unroll
     for (int t = 0; t < RT; ++t) epilogue<P, SPEC, l, MT>(acc[t], nrm);
     store_rows<RT, MT, FULL>(acc, a, row0, rows, lane);
@@ -313,11 +339,12 @@ __device__ __forceinline__ void run_first(const Args& a, const typename P::terms
   constexpr int N = S::N[0], MT = N / 32;
   const int h = lane >> 5;
   const float* bias = (const float*)(lds + S::boff(LM, 0));
+  constexpr bool BL = bias_last<S, SPEC, 0>();
   f32x16 acc[RT][MT];
 #pragma unroll
   for (int t = 0; t < RT; ++t)
 #pragma unroll
-    for (int m = 0; m < MT; ++m) acc[t][m] = ld_bias_frag(bias, m, h);
+    for (int m = 0; m < MT; ++m) acc[t][m] = BL ? zero16() : ld_bias_frag(bias, m, h);
   layer_x3<KS0, MT, MT, RT, x3_db<MT>()>(acc, src_of<S, LM, 0>(a, lds, lane), 0,
                                   [&](int s, int t) { return b0[t][s]; });
   if constexpr (S::NL > 1) {
@@ -325,6 +352,7 @@ __device__ __forceinline__ void run_first(const Args& a, const typename P::terms
     epilogue_next<P, SPEC, 0, MT, RT>(acc, nrm, pn);
     run_rest<P, S, SPEC, LM, 1, RT, MT, pend_kind<SPEC, 0>()>(a, acc, pn, lds, nrm, row0, rows, lane);
   } else {
+    if constexpr (BL) add_bias<RT, MT>(acc, bias, h);
 #pragma unroll
     for (int t = 0; t < RT; ++t) epilogue<P, SPEC, 0, MT>(acc[t], nrm);
     store_rows<RT, MT>(acc, a, row0, rows, lane);

@@ -197,6 +197,16 @@ def layer_array(specs: List[LayerSpec], base: int, offs: List[int], fmts=None):
     return arr
 
 
+def _shape_refusal(rows, out, *ins) -> bool:
+    """Whether a kernel's RG_ERR_UNSUPPORTED for this call can only be about the chain's shape,
+    so that ChainPlan may remember it: every tensor's rows contiguous or at a stride of a
+    multiple of 32 bytes, the output within 32-bit byte offsets.  The kernels also refuse other
+    strides and larger outputs, which says nothing about the plan's next call."""
+    ts = [t for t in (out,) + ins if t is not None]
+    return (all(t.stride(0) == t.shape[-1] or t.stride(0) % 8 == 0 for t in ts)
+            and int(rows) * out.stride(0) * 4 <= 0x7ff00000)
+
+
 class ChainPlan:
     """Packed weights + launch descriptors of one or more rg_mlp_chain calls."""
 
@@ -369,6 +379,7 @@ class ChainPlan:
                                      residual, rows_dev, segs)
         lib = nat.lib()
         st = nat.stream_ptr(self.device)
+        keep = lambda: _shape_refusal(rows, out, in0, in1, in2, residual)  # noqa: E731
         f32_fast = (self.use_fast and self.dt == nat.RG_F32 and mode in (nat.IN_DENSE, nat.IN_PAIRADD)
                     and residual is None and in0.dtype == torch.float32
                     and out.dtype == torch.float32 and len(self.specs) <= nat.MAX_LAYERS)
@@ -381,7 +392,8 @@ class ChainPlan:
                 return out
             if rc != nat.RG_ERR_UNSUPPORTED:
                 nat.check(rc, 'rg_mlp_chain_x3')
-            self.x3_ok[mode] = False
+            if keep():
+                self.x3_ok[mode] = False
         if f32_fast and self.fast_ok.get(mode, True):
             rc = lib.rg_mlp_chain_f32(self._f32_layers(), len(self.specs), int(rows),
                                       nat.ptr(rows_dev), mode, in0.data_ptr(), in0.stride(0), w0,
@@ -392,7 +404,8 @@ class ChainPlan:
                 return out
             if rc != nat.RG_ERR_UNSUPPORTED:
                 nat.check(rc, 'rg_mlp_chain_f32')
-            self.fast_ok[mode] = False
+            if keep():
+                self.fast_ok[mode] = False
         if self.use_fast and self.fast is not None and self.fast_ok.get(mode, True):
             rc = lib.rg_mlp_chain_fast(
                 self.fast, len(self.specs), int(rows), nat.ptr(rows_dev), mode, _dt_code(in0),
@@ -408,7 +421,8 @@ class ChainPlan:
                 return out
             if rc != nat.RG_ERR_UNSUPPORTED:
                 nat.check(rc, 'rg_mlp_chain_fast')
-            self.fast_ok[mode] = False
+            if keep():
+                self.fast_ok[mode] = False
         if self.groups is None:
             raise NotImplementedError(
                 f'fp16 chains run on the register-resident fast kernels only, which have no '

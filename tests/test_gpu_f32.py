@@ -37,7 +37,8 @@ def _torch_chain64(plan, x):
 @pytest.mark.parametrize('arith', ['x3', 'mfma_f32'])
 def test_f32_fast_chains_used_and_exact(cuda_device, arith, monkeypatch):
     """Every chain of the yml architecture in fp32 runs on its register-resident kernel --
-    rg_mlp_chain_x3 (f32 products from exact three-term bf16 splits) or rg_mlp_chain_f32
+    rg_mlp_chain_x3 (f32 products from split operands: the engine's default scheme, 'h2', two
+    fp16 terms and three products; 'b3' is held to the same in test_gpu_chain_x3.py) or rg_mlp_chain_f32
     (v_mfma_f32_32x32x2_f32) -- and agrees with the generic f32 kernel and with a float64
     evaluation (1e-4)."""
     from graph_neural_network_for_radar_perception_amd import _native as nat
@@ -114,7 +115,8 @@ def test_f32_chain_rows_dev_and_empty(cuda_device):
 
 @pytest.mark.parametrize('R', [1, 3001, 140_000])
 def test_x3_encoders_rows(cuda_device, R):
-    """The x3 encoders (chain_x3: f32 products from exact three-term bf16 splits) over one row,
+    """The x3 encoders (chain_x3 under the engine's default scheme, 'h2': two-term fp16 splits,
+    three products; both schemes per shape in test_gpu_chain_x3.py) over one row,
     a partial pass and several passes per workgroup: every sampled row at 1e-4 of a float64
     evaluation, deterministic across calls, and rows_dev bounds the rows written."""
     from graph_neural_network_for_radar_perception_amd.config import default_config
