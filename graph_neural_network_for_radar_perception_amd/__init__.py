@@ -9,8 +9,12 @@ Drop-in entry points (same names / signatures as the reference):
   graph_features.compute_adjacency_information / _v2,
   compute_node_features, compute_edge_features                 (graph_features.py)
   config.config                                                (set_config_gnn.py)
+  evaluation.compute_gt_and_pred_associations                  (detection_accuracy.py)
 Batched device path: graph_features.FrameBatch / build_graph_batch,
 pipeline.RadarGNNPipeline.
+Evaluation on the device (import from ``.evaluation``): evaluation.DetectionEvaluator
+(performance_eval_detection.ipynb: confusion matrix, precision, recall) and
+evaluation.SegmentationEvaluator (performance_eval_segmentation.ipynb).
 """
 from . import config, synthetic  # noqa: F401
 

@@ -125,6 +125,16 @@ _SIGNATURES = {
     'rg_cluster_pairs': (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _F, _I, _P, _P]),
     'rg_cluster_lists_workspace_size': (_S, [_I]),
     'rg_cluster_lists': (_I, [_P, _I, _P, _P, _P, _P, _P, _S, _P]),
+    # evaluation (evaluation.hip)
+    'rg_eval_gt_clusters_workspace_size': (_S, [_I]),
+    'rg_eval_gt_clusters': (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _S, _P]),
+    'rg_argmax_rows': (_I, [_P, _I, _L, _I, _P, _P]),
+    'rg_eval_cluster_of': (_I, [_P, _P, _I, _I, _P, _P]),
+    'rg_eval_associate_workspace_size': (_S, [_I, _I]),
+    'rg_eval_associate': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P,
+                               _P, _P, _P, _P, _P, _P, _P, _S, _P]),
+    'rg_eval_accumulate': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'rg_eval_node_confusion': (_I, [_P, _I, _P, _L, _I, _P, _P, _P, _P]),
     'rg_csr_by_dst_workspace_size': (_S, [_I, _L]),
     'rg_csr_by_dst': (_I, [_P, _L, _I, _P, _P, _P, _P, _S, _P]),
     'rg_dense_adjacency': (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),

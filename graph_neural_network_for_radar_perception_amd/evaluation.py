@@ -1,0 +1,500 @@
+"""Detection and segmentation evaluation on the GPU (csrc/evaluation.hip).
+
+The reference's evaluation (modules/performance/detection_accuracy.py,
+segmentation_accuracy.py, performance_eval_detection.ipynb, performance_eval_segmentation.ipynb)
+for batches of frames:
+
+  gt_clusters                        compute_node_idx_for_each_cluster (datagen_gnn.py:15-45)
+  associate                          the size filter of detection_accuracy.py:141-164 and
+                                     compute_gt_and_pred_associations (:192-273), all frames
+  compute_gt_and_pred_associations   the drop-in for the reference function (one frame)
+  DetectionEvaluator                 performance_eval_detection.ipynb: confusion matrix,
+                                     ground-truth and prediction counts, precision, recall
+  SegmentationEvaluator              performance_eval_segmentation.ipynb: node-level confusion
+
+The predicted node class is the argmax of the ``node_cls`` logits, lowest index on a tie.  The
+reference takes the argmax of the float32 softmax (detection_accuracy.py:97-98), which is the
+same class except where two logits within an ulp of each other round to equal probabilities:
+there the reference returns the lower index even when its logit is the smaller one.
+
+Counters live on the device as int64 tensors; ``update`` enqueues kernels on the current stream
+and never synchronises, ``result`` reads the counters back once.
+"""
+from __future__ import annotations
+
+import json
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _native as nat
+
+INVALID_CLS_IDX = 5  # the 'NONE' class both notebooks delete before reporting
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _i32(dev, n, fill=None):
+    torch = _torch()
+    if fill is None:
+        return torch.empty(max(int(n), 1), dtype=torch.int32, device=dev)
+    return torch.full((max(int(n), 1),), fill, dtype=torch.int32, device=dev)
+
+
+def _workspace(cache: Optional[dict], name: str, nbytes: int, dev):
+    torch = _torch()
+    cache = cache if cache is not None else {}
+    t = cache.get(name)
+    if t is None or t.numel() < nbytes or t.device != dev:
+        t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        cache[name] = t
+    return t
+
+
+def _rows(x):
+    """A float32 matrix with unit column stride (its row stride is passed as ld)."""
+    torch = _torch()
+    x = x.detach()
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    if x.dim() != 2:
+        raise ValueError(f'expected a [rows, classes] matrix, got {tuple(x.shape)}')
+    if x.shape[0] > 0 and x.stride(1) != 1:
+        x = x.contiguous()
+    return x
+
+
+def argmax_rows(x):
+    """int64 [rows]: the index of the first maximum of every row (rg_argmax_rows)."""
+    torch = _torch()
+    x = _rows(x)
+    n, nc = int(x.shape[0]), int(x.shape[1])
+    out = torch.empty(max(n, 1), dtype=torch.int64, device=x.device)
+    if n > 0:
+        nat.check(nat.lib().rg_argmax_rows(x.data_ptr(), x.stride(0), n, nc, out.data_ptr(),
+                                           nat.stream_ptr(x.device)), 'rg_argmax_rows')
+    return out[:n]
+
+
+def gt_clusters(track_key, node_class, frame_ptr, ws_cache: Optional[dict] = None) -> dict:
+    """Ground-truth clusters of a batch from per-node track keys (int32, 0 = no track): per
+    frame the tracked clusters in ascending key order, then one singleton per untracked node
+    (compute_node_idx_for_each_cluster, datagen_gnn.py:15-45).  Device tensors, no sync:
+    cluster_of [N], cluster_ptr [N+1] (entries past the last cluster repeat N), cluster_idx
+    [N], frame_clusters [F], cluster_class int64 [N], n_clusters [1]."""
+    torch = _torch()
+    dev = track_key.device
+    N, F = int(track_key.shape[0]), int(frame_ptr.shape[0]) - 1
+    lib = nat.lib()
+    key = track_key.to(torch.int32).contiguous()
+    cls = node_class.to(torch.int64).contiguous()
+    fptr = frame_ptr.to(torch.int32).contiguous()
+    out = dict(cluster_of=_i32(dev, N), cluster_ptr=_i32(dev, N + 1), cluster_idx=_i32(dev, N),
+               frame_clusters=_i32(dev, F),
+               cluster_class=torch.empty(max(N, 1), dtype=torch.int64, device=dev),
+               n_clusters=_i32(dev, 1))
+    wsz = lib.rg_eval_gt_clusters_workspace_size(N)
+    ws = _workspace(ws_cache, 'eval_gt_ws', wsz, dev)
+    nat.check(lib.rg_eval_gt_clusters(key.data_ptr(), cls.data_ptr(), fptr.data_ptr(), N, F,
+                                      out['cluster_of'].data_ptr(), out['cluster_ptr'].data_ptr(),
+                                      out['cluster_idx'].data_ptr(),
+                                      out['frame_clusters'].data_ptr(),
+                                      out['cluster_class'].data_ptr(),
+                                      out['n_clusters'].data_ptr(), ws.data_ptr(), wsz,
+                                      nat.stream_ptr(dev)), 'rg_eval_gt_clusters')
+    out['frame_clusters'] = out['frame_clusters'][:F]
+    return out
+
+
+def _full_ptr(cluster_ptr, N):
+    """cluster_ptr padded to N + 1 entries, the tail repeating N (the rg_cluster_lists form)."""
+    torch = _torch()
+    ptr = cluster_ptr.to(torch.int32)
+    if ptr.numel() > N + 1:
+        raise ValueError(f'{ptr.numel() - 1} clusters for {N} nodes')
+    if ptr.numel() == N + 1:
+        return ptr.contiguous()
+    full = torch.full((N + 1,), N, dtype=torch.int32, device=ptr.device)
+    full[:ptr.numel()] = ptr
+    return full
+
+
+def cluster_of(cluster_ptr, cluster_idx, N):
+    """int32 [N]: the cluster of every node of a CSR (-1 = in none)."""
+    dev = cluster_ptr.device
+    out = _i32(dev, N)
+    ncl = int(cluster_ptr.numel()) - 1
+    nat.check(nat.lib().rg_eval_cluster_of(cluster_ptr.data_ptr(), cluster_idx.data_ptr(), ncl, N,
+                                           out.data_ptr(), nat.stream_ptr(dev)),
+              'rg_eval_cluster_of')
+    return out
+
+
+def associate(frame_ptr, gt_of, gt_ptr, gt_idx, pred_of, pred_ptr, pred_idx, eps: float,
+              cluster_size_threshold: int = 0, max_frame_nodes: Optional[int] = None,
+              ws_cache: Optional[dict] = None) -> dict:
+    """Size filter + greedy 1 - IoU association of every frame (rg_eval_associate).  All
+    arguments are int32 device tensors over the batch's N nodes (``*_ptr`` with N + 1
+    entries).  Returns device tensors: gt_kept / pred_kept [N]; pick_start / pick_count [F];
+    pick_gt, pick_pred, pick_d, pick_positive, pick_gt_cluster, pick_pred_cluster [N] -- frame
+    f's picks, in pick order, are the slots pick_start[f] .. + pick_count[f]."""
+    torch = _torch()
+    dev = gt_of.device
+    N, F = int(gt_of.shape[0]), int(frame_ptr.shape[0]) - 1
+    lib = nat.lib()
+    out = dict(gt_kept=_i32(dev, N), pred_kept=_i32(dev, N), pick_start=_i32(dev, F),
+               pick_count=_i32(dev, F), pick_gt=_i32(dev, N), pick_pred=_i32(dev, N),
+               pick_d=torch.empty(max(N, 1), dtype=torch.float32, device=dev),
+               pick_positive=_i32(dev, N), pick_gt_cluster=_i32(dev, N),
+               pick_pred_cluster=_i32(dev, N))
+    wsz = lib.rg_eval_associate_workspace_size(N, F)
+    ws = _workspace(ws_cache, 'eval_assoc_ws', wsz, dev)
+    maxn = N if max_frame_nodes is None else int(max_frame_nodes)
+    nat.check(lib.rg_eval_associate(
+        frame_ptr.data_ptr(), N, F, maxn, gt_of.data_ptr(), gt_ptr.data_ptr(), gt_idx.data_ptr(),
+        pred_of.data_ptr(), pred_ptr.data_ptr(), pred_idx.data_ptr(), int(cluster_size_threshold),
+        float(eps), out['gt_kept'].data_ptr(), out['pred_kept'].data_ptr(),
+        out['pick_start'].data_ptr(), out['pick_count'].data_ptr(), out['pick_gt'].data_ptr(),
+        out['pick_pred'].data_ptr(), out['pick_d'].data_ptr(), out['pick_positive'].data_ptr(),
+        out['pick_gt_cluster'].data_ptr(), out['pick_pred_cluster'].data_ptr(), ws.data_ptr(), wsz,
+        nat.stream_ptr(dev)), 'rg_eval_associate')
+    for k in ('pick_start', 'pick_count'):
+        out[k] = out[k][:F]
+    for k in ('gt_kept', 'pred_kept', 'pick_gt', 'pick_pred', 'pick_d', 'pick_positive',
+              'pick_gt_cluster', 'pick_pred_cluster'):
+        out[k] = out[k][:N]
+    return out
+
+
+def frame_picks(assoc: dict) -> List[dict]:
+    """The picks of ``associate`` per frame, on the host (one synchronisation): a list of
+    dicts with gt, pred (int32), d (float32) and positive (bool) arrays in pick order."""
+    h = {k: v.cpu().numpy() for k, v in assoc.items() if k.startswith('pick_')}
+    out = []
+    for s, c in zip(h['pick_start'], h['pick_count']):
+        sl = slice(int(s), int(s) + int(c))
+        out.append(dict(gt=h['pick_gt'][sl].copy(), pred=h['pick_pred'][sl].copy(),
+                        d=h['pick_d'][sl].copy(), positive=h['pick_positive'][sl] != 0))
+    return out
+
+
+def _csr_from_sets(sets: Sequence[set], remap: dict, N: int, what: str):
+    of = np.full(max(N, 1), -1, dtype=np.int32)
+    ptr = np.full(N + 1, N, dtype=np.int32)
+    idx = np.zeros(max(N, 1), dtype=np.int32)
+    pos = 0
+    for c, s in enumerate(sets):
+        if len(s) == 0:
+            raise ValueError(f'{what} cluster {c} is empty (the reference divides by zero)')
+        mem = sorted(remap[v] for v in s)
+        ptr[c] = pos
+        for m in mem:
+            if of[m] != -1:
+                raise ValueError(f'{what} clusters {of[m]} and {c} share a measurement')
+            of[m] = c
+        idx[pos:pos + len(mem)] = mem
+        pos += len(mem)
+    ptr[len(sets):] = pos
+    return of, ptr, idx, pos
+
+
+def compute_gt_and_pred_associations(det_and_gt_clusters, eps, association_criteria='inv_iou',
+                                     false_class_label=6, device=None):
+    """Drop-in for detection_accuracy.compute_gt_and_pred_associations (:192-273): the same
+    dict of lists in, the same four numpy arrays out, element for element; the association
+    runs on the GPU.  'l2_norm' (a dense matrix the notebooks do not use) is not built."""
+    torch = _torch()
+    if association_criteria == 'l2_norm':
+        raise NotImplementedError("association_criteria='l2_norm' is not implemented "
+                                  "(the evaluation notebooks use 'inv_iou')")
+    if association_criteria != 'inv_iou':
+        raise ValueError(f'association_criteria {association_criteria!r}')
+    d = det_and_gt_clusters
+    n_pred, n_gt = len(d['cluster_mean_list_pred']), len(d['cluster_mean_list_gt'])
+    empty = np.zeros(shape=(0, ))
+    if n_pred == 0 or n_gt == 0:
+        return {'obj_class_gt_associated': empty, 'obj_class_pred_associated': empty,
+                'obj_class_gt': np.array(d['obj_class_gt']) if n_gt > 0 else empty,
+                'obj_class_pred': np.array(d['obj_class_pred']) if n_pred > 0 else empty}
+    obj_class_pred = np.array(d['obj_class_pred'])
+    obj_class_gt = np.array(d['obj_class_gt'])
+    gt_sets, pred_sets = d['cluster_member_list_gt'], d['cluster_member_list_pred']
+    universe = sorted(set().union(*gt_sets, *pred_sets))
+    remap = {v: i for i, v in enumerate(universe)}
+    N = len(universe)
+    dev = torch.device(device) if device is not None else torch.device('cuda',
+                                                                       torch.cuda.current_device())
+    g_of, g_ptr, g_idx, g_n = _csr_from_sets(gt_sets, remap, N, 'ground-truth')
+    p_of, p_ptr, p_idx, p_n = _csr_from_sets(pred_sets, remap, N, 'predicted')
+    # a side that does not cover every node leaves the tail of its member list unused
+    up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    fptr = up(np.array([0, N], dtype=np.int32))
+    res = associate(fptr, up(g_of), up(g_ptr), up(g_idx), up(p_of), up(p_ptr), up(p_idx),
+                    float(eps), cluster_size_threshold=0)
+    pk = frame_picks(res)[0]
+    pos = pk['positive']
+    gi, pi = pk['gt'].astype(np.int64), pk['pred'].astype(np.int64)
+    pos_gt = obj_class_gt[gi[pos]]
+    pos_pred = obj_class_pred[pi[pos]]
+    neg_pred = obj_class_pred[pi[~pos]]
+    neg_gt = np.repeat(false_class_label, repeats=neg_pred.shape[0])
+    return {'obj_class_gt_associated': np.concatenate((pos_gt, neg_gt), axis=0),
+            'obj_class_pred_associated': np.concatenate((pos_pred, neg_pred), axis=0),
+            'obj_class_gt': obj_class_gt, 'obj_class_pred': obj_class_pred}
+
+
+# ------------------------------------------------------------------------- reporting
+def _drop(a: np.ndarray, index: Optional[int], axes) -> np.ndarray:
+    if index is None or index >= a.shape[0]:
+        return a
+    for ax in axes:
+        a = np.delete(a, index, axis=ax)
+    return a
+
+
+def detection_report(confusion, gt_count, pred_count, invalid_class_index=INVALID_CLS_IDX) -> dict:
+    """performance_eval_detection.ipynb, the summary cell: class ``invalid_class_index`` dropped
+    from rows and columns, the row-normalised confusion matrix in percent, precision =
+    diag / pred_count, recall = diag / gt_count (0 / 0 is nan, as in the notebook)."""
+    conf = _drop(np.asarray(confusion, dtype=np.uint64), invalid_class_index, (0, 1))
+    gt = _drop(np.asarray(gt_count, dtype=np.uint64), invalid_class_index, (0,))
+    pred = _drop(np.asarray(pred_count, dtype=np.uint64), invalid_class_index, (0,))
+    idx = np.arange(conf.shape[0])
+    with np.errstate(divide='ignore', invalid='ignore'):
+        norm = conf / np.sum(conf, axis=-1, keepdims=True) * 100
+        precision = conf[idx, idx] / pred
+        recall = conf[idx, idx] / gt
+    return {'normalized_confusion_matrix': norm, 'precision': precision, 'recall': recall}
+
+
+def segmentation_report(confusion, gt_count, invalid_class_index=INVALID_CLS_IDX) -> dict:
+    """performance_eval_segmentation.ipynb, the summary cell: class ``invalid_class_index``
+    dropped, each row divided by its ground-truth count, in percent, float32; a row without
+    ground truth is 0."""
+    conf = _drop(np.asarray(confusion, dtype=np.uint64), invalid_class_index, (0, 1))
+    gt = _drop(np.asarray(gt_count, dtype=np.uint64), invalid_class_index, (0,))
+    norm = np.zeros(conf.shape, dtype=np.float32)
+    for i in range(gt.shape[0]):
+        num_gt = gt[i]
+        if num_gt > 0:
+            norm[i, :] = conf[i, :] / num_gt * 100
+        else:
+            norm[i, :] = 0.0
+    return {'confusion_matrix_norm': norm}
+
+
+class _Counters:
+    """int64 counters: a device tensor per name, created by the first update, plus a host part
+    (merged evaluators).  ``counts`` synchronises once."""
+
+    NAMES: tuple = ()
+
+    def __init__(self, num_classes: int):
+        if not 1 <= int(num_classes) <= 32:
+            raise ValueError(f'num_classes={num_classes} outside 1..32')
+        self.num_classes = int(num_classes)
+        self._host = {k: np.zeros(self._shape(k), dtype=np.int64) for k in self.NAMES}
+        self._dev = None
+        self._bad = None
+        self._ws: dict = {}
+
+    def _shape(self, name):
+        nc = self.num_classes
+        return (nc, nc) if name == 'confusion_matrix' else (nc,)
+
+    def _device_counters(self, dev):
+        torch = _torch()
+        if self._dev is None:
+            self._dev = {k: torch.zeros(self._shape(k), dtype=torch.int64, device=dev)
+                         for k in self.NAMES}
+            self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        elif self._bad.device != dev:
+            raise ValueError(f'evaluator lives on {self._bad.device}, update came from {dev}')
+        return self._dev
+
+    def counts(self) -> dict:
+        out = {k: v.copy() for k, v in self._host.items()}
+        if self._dev is not None:
+            torch = _torch()
+            flat = torch.cat([self._dev[k].reshape(-1) for k in self.NAMES]
+                             + [self._bad.to(torch.int64)]).cpu().numpy()
+            if flat[-1]:
+                raise RuntimeError('a class id outside [0, num_classes) reached the evaluator')
+            off = 0
+            for k in self.NAMES:
+                n = int(np.prod(self._shape(k)))
+                out[k] += flat[off:off + n].reshape(self._shape(k))
+                off += n
+        return {k: v.astype(np.uint64) for k, v in out.items()}
+
+    def merge(self, other):
+        """Add another evaluator's counters (another rank's, another sequence's)."""
+        if type(other) is not type(self) or other.num_classes != self.num_classes:
+            raise ValueError('merge needs an evaluator of the same kind and num_classes')
+        for k, v in other.counts().items():
+            self._host[k] += v.astype(np.int64)
+        return self
+
+    def load_counts(self, **counts):
+        """Add host count matrices (for instance read back from ``to_json`` files)."""
+        for k in self.NAMES:
+            a = np.asarray(counts[k], dtype=np.int64)
+            if a.shape != self._shape(k):
+                raise ValueError(f'{k}: shape {a.shape}, expected {self._shape(k)}')
+            self._host[k] += a
+        return self
+
+    def to_json(self, path, class_names):
+        """The reference's per-sequence file: class_names and the count matrices as lists."""
+        data = {'class_names': list(class_names)}
+        for k, v in self.counts().items():
+            data[k] = v.tolist()
+        with open(path, 'w') as fh:
+            json.dump(data, fh, indent=4)
+        return data
+
+
+class DetectionEvaluator(_Counters):
+    """performance_eval_detection.ipynb on the device: per batch the ground-truth clusters from
+    the track keys, the predicted clusters' classes, the size filter, the greedy 1 - IoU
+    association (compute_gt_and_pred_associations) and the three count matrices."""
+
+    NAMES = ('confusion_matrix', 'gt_count_matrix', 'pred_count_matrix')
+
+    def __init__(self, num_classes: int = 7, eps: float = 0.7, cluster_size_threshold: int = 0,
+                 by_segmentation: bool = True, false_class_label: int = 6):
+        super().__init__(num_classes)
+        if not 0 <= int(false_class_label) < self.num_classes:
+            raise ValueError(f'false_class_label={false_class_label} outside [0, {num_classes})')
+        if int(cluster_size_threshold) < 0:
+            raise ValueError('cluster_size_threshold < 0')
+        self.eps = float(eps)
+        self.cluster_size_threshold = int(cluster_size_threshold)
+        self.by_segmentation = bool(by_segmentation)
+        self.false_class_label = int(false_class_label)
+
+    def update(self, node_cls, obj_cls, pred_cluster_ptr, pred_cluster_idx, node_gt_class,
+               track_key, frame_ptr, max_frame_nodes: Optional[int] = None):
+        """One batch, every tensor on the device, no host synchronisation.  node_cls f32
+        [N, C] logits, obj_cls f32 [clusters, C] logits (read only when not by_segmentation),
+        pred_cluster_ptr / pred_cluster_idx the predicted clusters' CSR over global node ids
+        (as engine.propose_clusters returns them), node_gt_class [N], track_key int32 [N]
+        (0 = no track), frame_ptr int32 [F + 1].  max_frame_nodes bounds the largest frame
+        (default: N); it must stay below 2^24.  ``self.last`` keeps the batch's device
+        tensors (ground-truth clusters, predicted classes, picks) until the next update."""
+        torch = _torch()
+        dev = node_cls.device
+        if dev.type != 'cuda':
+            raise ValueError('DetectionEvaluator.update needs device tensors')
+        lib = nat.lib()
+        st = nat.stream_ptr(dev)
+        acc = self._device_counters(dev)
+        N, F = int(node_cls.shape[0]), int(frame_ptr.shape[0]) - 1
+        if N == 0 or F <= 0:
+            return self
+        fptr = frame_ptr.to(torch.int32).contiguous()
+        gt = gt_clusters(track_key, node_gt_class, fptr, self._ws)
+        ncl = int(pred_cluster_ptr.numel()) - 1
+        p_ptr = _full_ptr(pred_cluster_ptr, N)
+        p_idx = pred_cluster_idx.to(torch.int32).contiguous()
+        p_of = cluster_of(p_ptr, p_idx, N)
+        if self.by_segmentation:
+            node_pred = argmax_rows(node_cls)
+            p_cls = torch.empty(max(ncl, 1), dtype=torch.int64, device=dev)
+            nat.check(lib.rg_cluster_majority_label(node_pred.data_ptr(), p_ptr.data_ptr(),
+                                                    p_idx.data_ptr(), ncl, self.num_classes,
+                                                    p_cls.data_ptr(), self._bad.data_ptr(), st),
+                      'rg_cluster_majority_label')
+        else:
+            if int(obj_cls.shape[0]) < ncl:
+                raise ValueError(f'obj_cls has {obj_cls.shape[0]} rows for {ncl} clusters')
+            p_cls = argmax_rows(obj_cls) if ncl > 0 else torch.zeros(1, dtype=torch.int64,
+                                                                     device=dev)
+        res = associate(fptr, gt['cluster_of'], gt['cluster_ptr'], gt['cluster_idx'], p_of, p_ptr,
+                        p_idx, self.eps, self.cluster_size_threshold, max_frame_nodes, self._ws)
+        nat.check(lib.rg_eval_accumulate(
+            res['pick_gt_cluster'].data_ptr(), res['pick_pred_cluster'].data_ptr(),
+            res['pick_positive'].data_ptr(), res['gt_kept'].data_ptr(),
+            res['pred_kept'].data_ptr(), gt['cluster_class'].data_ptr(), p_cls.data_ptr(), N,
+            self.num_classes, self.false_class_label, acc['confusion_matrix'].data_ptr(),
+            acc['gt_count_matrix'].data_ptr(), acc['pred_count_matrix'].data_ptr(),
+            self._bad.data_ptr(), st), 'rg_eval_accumulate')
+        self.last = dict(gt=gt, pred_class=p_cls[:ncl], assoc=res)
+        return self
+
+    def update_frames(self, detector_outputs, node_gt_class, track_key):
+        """A batch straight from ``Model_Inference.forward_frames(..., cluster_node_idx=None,
+        other_features)``: its 5-tuple (node_cls, node_reg, link_cls, obj_cls, per-frame lists
+        of frame-local member indices), with the per-frame lists of ground-truth node classes
+        and track keys."""
+        torch = _torch()
+        node_cls, _, _, obj_cls, lists = detector_outputs
+        dev = node_cls.device
+        sizes = [int(t.shape[0]) for t in node_gt_class]
+        if len(lists) != len(sizes) or len(track_key) != len(sizes):
+            raise ValueError('one cluster list, class tensor and key tensor per frame')
+        bases = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+        members, counts = [], []
+        for f, frame in enumerate(lists):
+            for m in frame:
+                members.append(m.to(dev, torch.int64) + int(bases[f]))
+                counts.append(int(m.shape[0]))
+        N = int(bases[-1])
+        idx = (torch.cat(members) if members else torch.zeros(0, dtype=torch.int64, device=dev))
+        idx = idx.to(torch.int32)
+        if idx.numel() < N:  # nodes in no cluster: pad the member list to its [N] form
+            idx = torch.cat([idx, torch.zeros(N - idx.numel(), dtype=torch.int32, device=dev)])
+        ptr = torch.from_numpy(np.concatenate(([0], np.cumsum(counts))).astype(np.int32)).to(dev)
+        fptr = torch.from_numpy(bases.astype(np.int32)).to(dev)
+        cat = lambda ts, dt: torch.cat([torch.as_tensor(t).reshape(-1).to(dev, dt)  # noqa: E731
+                                        for t in ts]) if ts else torch.zeros(0, dtype=dt, device=dev)
+        return self.update(node_cls, obj_cls, ptr, idx, cat(node_gt_class, torch.int64),
+                           cat(track_key, torch.int32), fptr,
+                           max_frame_nodes=max(sizes) if sizes else 0)
+
+    def result(self, invalid_class_index: Optional[int] = INVALID_CLS_IDX) -> dict:
+        """One synchronisation: the three count matrices (numpy uint64) and the notebook's
+        precision, recall and normalized_confusion_matrix (class 5 dropped)."""
+        out = self.counts()
+        out.update(detection_report(out['confusion_matrix'], out['gt_count_matrix'],
+                                    out['pred_count_matrix'], invalid_class_index))
+        return out
+
+
+class SegmentationEvaluator(_Counters):
+    """performance_eval_segmentation.ipynb on the device: confusion[gt class, predicted class]
+    and gt_count over the nodes of every batch."""
+
+    NAMES = ('confusion_matrix', 'gt_count_matrix')
+
+    def __init__(self, num_classes: int = 7):
+        super().__init__(num_classes)
+
+    def update(self, node_cls, node_gt_class):
+        """node_cls f32 [N, C] logits and node_gt_class [N] on the device; no host sync."""
+        torch = _torch()
+        x = _rows(node_cls)
+        dev = x.device
+        if dev.type != 'cuda':
+            raise ValueError('SegmentationEvaluator.update needs device tensors')
+        if int(x.shape[1]) != self.num_classes:
+            raise ValueError(f'node_cls has {x.shape[1]} classes, evaluator {self.num_classes}')
+        acc = self._device_counters(dev)
+        gt = node_gt_class.to(dev, torch.int64).reshape(-1).contiguous()
+        if gt.numel() != x.shape[0]:
+            raise ValueError(f'{x.shape[0]} rows of logits, {gt.numel()} classes')
+        nat.check(nat.lib().rg_eval_node_confusion(
+            x.data_ptr(), x.stride(0) if x.shape[0] > 0 else self.num_classes, gt.data_ptr(),
+            int(x.shape[0]), self.num_classes, acc['confusion_matrix'].data_ptr(),
+            acc['gt_count_matrix'].data_ptr(), self._bad.data_ptr(), nat.stream_ptr(dev)),
+            'rg_eval_node_confusion')
+        return self
+
+    def result(self, invalid_class_index: Optional[int] = INVALID_CLS_IDX) -> dict:
+        out = self.counts()
+        out.update(segmentation_report(out['confusion_matrix'], out['gt_count_matrix'],
+                                       invalid_class_index))
+        return out

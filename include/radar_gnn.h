@@ -746,6 +746,69 @@ int rg_cluster_lists(const int* labels, int n_nodes, int* cluster_of, int* clust
                      int* cluster_idx, int* n_clusters, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---------------------------------------------------------------- evaluation */
+/* Detection and segmentation evaluation (modules/performance/detection_accuracy.py,
+ * performance_eval_detection.ipynb, performance_eval_segmentation.ipynb) for a batch of
+ * frames: global node ids and frame_ptr int32 [n_frames + 1] as rg_cluster_radius, every
+ * launch on the given stream, no host synchronisation.  Cluster CSRs have the form of
+ * rg_cluster_lists: cluster_ptr int32 [N + 1] whose entries past the last cluster repeat N,
+ * clusters ordered by frame. */
+
+/* compute_node_idx_for_each_cluster (datagen_gnn.py:15-45) from track_key int32 [N] (0 = no
+ * track; keys rank the sorted unique track ids, so ascending keys are np.unique's order):
+ * per frame the tracked clusters in ascending key order, then one singleton per untracked
+ * node in node order; members ascending; cluster_class int64 [N] = node_class of the lowest
+ * member.  frame_clusters int32 [n_frames] = clusters per frame, *n_clusters device int. */
+size_t rg_eval_gt_clusters_workspace_size(int n_nodes);
+int rg_eval_gt_clusters(const int* track_key, const int64_t* node_class, const int* frame_ptr,
+                        int n_nodes, int n_frames, int* cluster_of, int* cluster_ptr,
+                        int* cluster_idx, int* frame_clusters, int64_t* cluster_class,
+                        int* n_clusters, void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[r] = index of the first maximum of row r of x (float32 [n_rows][ld]); the predicted
+ * class of detection_accuracy.py:97-98 / 108-109 without the softmax. */
+int rg_argmax_rows(const float* x, int ld, long n_rows, int n_cols, int64_t* out, void* stream);
+
+/* cluster_of int32 [n_nodes] of a cluster CSR (cluster_ptr int32 [n_clusters + 1]): the
+ * cluster of every member, -1 for a node in none. */
+int rg_eval_cluster_of(const int* cluster_ptr, const int* cluster_idx, int n_clusters,
+                       int n_nodes, int* cluster_of, void* stream);
+
+/* compute_gt_and_pred_associations (detection_accuracy.py:192-273, 'inv_iou') after the size
+ * filter of detection_accuracy.py:141-164 (a cluster is kept when size > size_threshold),
+ * for every frame at once.  *_of int32 [N] (-1 = in no cluster), *_ptr int32 [N + 1], *_idx
+ * int32 [N].  Outputs: gt_kept / pred_kept int32 [N] flags per cluster; per frame f its picks
+ * in pick order at slots [pick_start[f], pick_start[f] + pick_count[f]) of the [N] arrays:
+ * pick_gt / pick_pred = indices among the frame's kept clusters, pick_d = float32(1 - IoU),
+ * pick_positive = d <= eps, pick_gt_cluster / pick_pred_cluster = the cluster ids in the CSRs
+ * (-1 in every unused slot).  A frame without a kept cluster on either side has no picks.
+ * max_frame_nodes >= 2^24 returns RG_ERR_UNSUPPORTED (1 - 1/union would round to 1.0f). */
+size_t rg_eval_associate_workspace_size(int n_nodes, int n_frames);
+int rg_eval_associate(const int* frame_ptr, int n_nodes, int n_frames, int max_frame_nodes,
+                      const int* gt_of, const int* gt_ptr, const int* gt_idx, const int* pred_of,
+                      const int* pred_ptr, const int* pred_idx, int size_threshold, float eps,
+                      int* gt_kept, int* pred_kept, int* pick_start, int* pick_count,
+                      int* pick_gt, int* pick_pred, float* pick_d, int* pick_positive,
+                      int* pick_gt_cluster, int* pick_pred_cluster, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* performance_eval_detection.ipynb: confusion[gt][pred] += 1 per pick (a negative pick's gt
+ * class is false_class), gt_count[class] += 1 per kept ground-truth cluster, pred_count[class]
+ * += 1 per kept predicted cluster; int64 device accumulators ([nc][nc], [nc], [nc]) kept by
+ * the caller across batches.  *bad_class (device int32, caller-zeroed) is set when a class
+ * is outside [0, num_classes).  num_classes outside 1..32: RG_ERR_UNSUPPORTED. */
+int rg_eval_accumulate(const int* pick_gt_cluster, const int* pick_pred_cluster,
+                       const int* pick_positive, const int* gt_kept, const int* pred_kept,
+                       const int64_t* gt_class, const int64_t* pred_class, int n_nodes,
+                       int num_classes, int false_class, int64_t* confusion, int64_t* gt_count,
+                       int64_t* pred_count, int* bad_class, void* stream);
+
+/* performance_eval_segmentation.ipynb: confusion[node_class][argmax(node_logits)] += 1 and
+ * gt_count[node_class] += 1 over all nodes; accumulators and bad_class as above. */
+int rg_eval_node_confusion(const float* node_logits, int ld, const int64_t* node_class,
+                           long n_nodes, int num_classes, int64_t* confusion, int64_t* gt_count,
+                           int* bad_class, void* stream);
+
 
 /* ------------------------------------------------------------------ training */
 /* The backward of the hot path (Model_Training + Loss_Graph + loss.backward(),
