@@ -10,11 +10,15 @@ Drop-in entry points (same names / signatures as the reference):
   compute_node_features, compute_edge_features                 (graph_features.py)
   config.config                                                (set_config_gnn.py)
   evaluation.compute_gt_and_pred_associations                  (detection_accuracy.py)
+  objects.compute_proposals, objects.compute_cov_ellipse       (inference.py, ellipse.py)
 Batched device path: graph_features.FrameBatch / build_graph_batch,
 pipeline.RadarGNNPipeline.
 Evaluation on the device (import from ``.evaluation``): evaluation.DetectionEvaluator
 (performance_eval_detection.ipynb: confusion matrix, precision, recall) and
 evaluation.SegmentationEvaluator (performance_eval_segmentation.ipynb).
+Object stage on the device (import from ``.objects``): objects.object_list (process_frame's
+numbers), objects.classifier_inputs (the classifier's training_data from the detector's
+clusters) and objects.classify_proposals (detector -> classifier, no host loop).
 """
 from . import config, synthetic  # noqa: F401
 

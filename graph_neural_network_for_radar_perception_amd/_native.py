@@ -135,6 +135,16 @@ _SIGNATURES = {
                                _P, _P, _P, _P, _P, _P, _P, _S, _P]),
     'rg_eval_accumulate': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     'rg_eval_node_confusion': (_I, [_P, _I, _P, _L, _I, _P, _P, _P, _P]),
+    # object stage (objects.hip)
+    'rg_cluster_stats': (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'rg_cov_ellipse': (_I, [_P, _P, _P, _I, _F, _I, _P, _P, _P]),
+    'rg_softmax_max': (_I, [_P, _I, _L, _I, _P, _P, _P]),
+    'rg_object_select_workspace_size': (_S, [_I]),
+    'rg_object_select': (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _S,
+                              _P]),
+    'rg_object_gather': (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P,
+                              _P, _P, _P, _P]),
+    'rg_object_features': (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     'rg_csr_by_dst_workspace_size': (_S, [_I, _L]),
     'rg_csr_by_dst': (_I, [_P, _L, _I, _P, _P, _P, _P, _S, _P]),
     'rg_dense_adjacency': (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),

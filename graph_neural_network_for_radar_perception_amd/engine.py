@@ -1445,6 +1445,7 @@ def propose_clusters(node_reg: torch.Tensor, other_xy: torch.Tensor, frame_ptr: 
                                       N, float(mu[0]), float(mu[1]), float(sigma[0]),
                                       float(sigma[1]), cx.data_ptr(), cy.data_ptr(), st),
               'rg_proposal_centres')
+    cache['proposal_centres'] = (cx[:N], cy[:N])  # objects.detect exposes them
     labels = torch.empty(max(N, 1), **i32)
     if from_links:
         if g is None or link_cls is None:

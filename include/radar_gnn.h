@@ -809,6 +809,75 @@ int rg_eval_node_confusion(const float* node_logits, int ld, const int64_t* node
                            long n_nodes, int num_classes, int64_t* confusion, int64_t* gt_count,
                            int* bad_class, void* stream);
 
+/* ------------------------------------------------------------------ object stage */
+/* From the detector's clusters to the classifier's inputs and the object list
+ * (modules/inference/inference.py, ellipse.py, output.py:99-171,
+ * data_generator/datagen_classifier.py:35-124, 166-190) for a batch of frames: global node
+ * ids, frame_ptr int32 [n_frames + 1], cluster CSRs of the rg_cluster_lists form (clusters
+ * ordered by frame, none empty).  Every launch on the given stream, no host synchronisation;
+ * matrices are row-major float32. */
+
+/* compute_cluster_sample_mean_and_cov (inference.py:23-30) of every cluster from xy f32
+ * [N][ld_xy]: size int32 [K], mu [K][2] = (sum p) / n, sigma [K][2][2] = sum (mu - p)(mu - p)^T
+ * / (n - 1) + noise_cov (n == 1: noise_cov).  noise_cov: HOST float32 [4], symmetric.  Sums run
+ * over the members in list order in float32 without contraction: bit-identical to numpy.
+ * eigval [K][2] / eigvec [K][2][2] (columns; both nullable): np.linalg.eig of sigma in float32,
+ * in LAPACK's order and sign (slanv2).  *bad_index (device int32, caller-zeroed, nullable) is
+ * set when a member or an offset lies outside [0, n_nodes]. */
+int rg_cluster_stats(const float* xy, int ld_xy, int n_nodes, const int* cluster_ptr,
+                     const int* cluster_idx, int n_clusters, const float* noise_cov, int* size,
+                     float* mu, float* sigma, float* eigval, float* eigvec, int* bad_index,
+                     void* stream);
+
+/* compute_cov_ellipse (ellipse.py:4-37) as written: abt [K][3] = half-axes a = chi_sq
+ * sqrt(largest eigenvalue), b = chi_sq sqrt(smallest), theta = atan2(v[l][1], v[l][0]) of ROW
+ * l = index of the largest eigenvalue (pi / 2 when v[l][0] == 0); points [K][n_points][2]
+ * (nullable; needs mu) = [a cos th, b sin th] @ R^T + mu over th = linspace(0, 2 pi,
+ * n_points).  n_points < 1: RG_ERR_ARG. */
+int rg_cov_ellipse(const float* eigval, const float* eigvec, const float* mu, int n_clusters,
+                   float chi_sq, int n_points, float* abt, float* points, void* stream);
+
+/* torch.max(F.softmax(x, -1), -1) of output.py:104-121 per row of x f32 [n_rows][ld]: cls int64
+ * = first maximum of the logits (as rg_argmax_rows), score f32 = its float32 softmax value
+ * (either nullable).  num_classes outside 1..32: RG_ERR_UNSUPPORTED. */
+int rg_softmax_max(const float* x, int ld, long n_rows, int num_classes, int64_t* cls,
+                   float* score, void* stream);
+
+/* remove_low_quality_proposals (datagen_classifier.py:166-190: kept when size >= min_meas) and
+ * the class filter of output.py:123-128 (cluster_class[c] == drop_class is dropped; -1 = no
+ * class filter), compacted on the device.  cluster_row int32 [K] = first member row of a kept
+ * cluster, -1 otherwise; obj_cluster int32 [K] = source cluster of kept object o; obj_row_ptr
+ * int32 [K + 1] = member rows of object o at [obj_row_ptr[o], obj_row_ptr[o + 1]);
+ * frame_obj_ptr / frame_row_ptr int32 [n_frames + 1] (nullable together) = each frame's range
+ * of kept objects / member rows; counts: device int64 [3] = kept objects K', member rows M',
+ * edges E' = sum n (n - 1) of the per-object complete graphs. */
+size_t rg_object_select_workspace_size(int n_clusters);
+int rg_object_select(const int* cluster_ptr, const int* cluster_idx, int n_clusters,
+                     const int* frame_ptr, int n_frames, const int64_t* cluster_class,
+                     int num_classes, int min_meas, int drop_class, int* cluster_row,
+                     int* obj_cluster, int* obj_row_ptr, int* frame_obj_ptr, int* frame_row_ptr,
+                     int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Rows of the kept objects o < counts[0] from the per-cluster arrays, c = obj_cluster[o]:
+ * obj_size int64 (object_num_meas), obj_class int64, obj_score, obj_mu [.][2], obj_sigma
+ * [.][2][2], obj_ellipse [.][3], obj_frame int32 (the frame of the first member).  Every
+ * output is nullable; its source must be given. */
+int rg_object_gather(const int* obj_cluster, const int64_t* counts, int n_clusters,
+                     const int* size, const int64_t* cluster_class, const float* score,
+                     const float* mu, const float* sigma, const float* ellipse,
+                     const int* cluster_ptr, const int* cluster_idx, const int* frame_ptr,
+                     int n_frames, int64_t* obj_size, int64_t* obj_class, float* obj_score,
+                     float* obj_mu, float* obj_sigma, float* obj_ellipse, int* obj_frame,
+                     void* stream);
+
+/* extract_and_compute_features_and_labels (datagen_classifier.py:62-100): features f32 [M'][5],
+ * one row per member of a kept cluster at cluster_row[c] + its position in the list:
+ * (x, y) = (p - mu) @ eigvec, r = sqrt(x^2 + y^2), th = atan2(y, x), rcs[node * ld_rcs]. */
+int rg_object_features(const float* xy, int ld_xy, const float* rcs, int ld_rcs, int n_nodes,
+                       const int* cluster_ptr, const int* cluster_idx, int n_clusters,
+                       const int* cluster_row, const float* mu, const float* eigvec,
+                       float* features, void* stream);
+
 
 /* ------------------------------------------------------------------ training */
 /* The backward of the hot path (Model_Training + Loss_Graph + loss.backward(),
