@@ -106,6 +106,8 @@ class LayerSpec:
     groups: int = 1
     center: bool = False    # pack zero-mean over the outputs although this layer has no norm
                             # (its outputs are summed into a normalised pre-activation later)
+    centered: bool = False  # the weights already are zero-mean over the outputs (centred by the
+                            # caller): marked in the descriptor, not centred again by the packer
 
     @property
     def frame_norm(self) -> bool:
@@ -156,45 +158,188 @@ def specs_from_modules(mods) -> List[LayerSpec]:
     return out
 
 
-def pack_specs(specs: List[LayerSpec], fmts: List[int], device):
-    """Pack layers (format fmts[i]) into one device buffer; returns (buffer, offsets)."""
-    lib = nat.lib()
-    sizes = [lib.rg_packed_linear_bytes(s.in_dim, s.out_dim, f) for s, f in zip(specs, fmts)]
-    offs, tot = [], 0
-    for sz in sizes:
-        offs.append(tot)
-        tot += (sz + 255) // 256 * 256
-    buf = torch.empty(tot, dtype=torch.uint8, device=device)
-    st = nat.stream_ptr(device)
-    base = buf.data_ptr()
-    for s, off, f in zip(specs, offs, fmts):
-        w = s.weight.detach().to(torch.float32).contiguous()
-        b = None if s.bias is None else s.bias.detach().to(torch.float32).contiguous()
-        nat.check(lib.rg_pack_linear(w.data_ptr(), nat.ptr(b), s.in_dim, s.out_dim, f,
-                                     base + off, st), 'rg_pack_linear')
-    return buf, offs
-
-
 def centered_fmt(spec: LayerSpec, fmt: int) -> int:
     """Fast formats of a normalised layer are packed zero-mean over the outputs
     (RG_PACK_CENTERED): the kernels' channel_normalization then skips its mean pass."""
     return fmt | nat.RG_PACK_CENTERED if (spec.mu is not None or spec.center) else fmt
 
 
+def _describe(d, packed: int, in_dim: int, out_dim: int, spec: Optional[LayerSpec], fmt: int):
+    """Fill one rg_layer; spec None: a bare Linear (no norm, no activation, no flags)."""
+    d.w_packed, d.in_dim, d.out_dim = packed, in_dim, out_dim
+    d.act = nat.ACT[spec.act if spec is not None else 'none']
+    if spec is not None:
+        d.norm_mu = nat.ptr(spec.mu.detach()) if spec.mu is not None else None
+        d.norm_std = nat.ptr(spec.std.detach()) if spec.std is not None else None
+        d.flags = ((nat.RG_LAYER_CENTERED if fmt & nat.RG_PACK_CENTERED or spec.centered else 0)
+                   | (nat.RG_LAYER_F16 if fmt & nat.RG_PACK_F16 else 0)
+                   | (nat.RG_LAYER_H2 if fmt & nat.RG_PACK_H2 else 0))
+
+
+def pack_specs(specs: List[LayerSpec], fmts: List[int], device):
+    """Pack layers (format fmts[i]) outside any plan; returns (buffer, offsets)."""
+    held = PackedImages(specs, device)._pack(tuple(fmts), False, None, None)
+    return held.buf, [im.packed - held.buf.data_ptr() for im in held.images]
+
+
 def layer_array(specs: List[LayerSpec], base: int, offs: List[int], fmts=None):
+    """Descriptors of layers packed by pack_specs at base + offs[i]."""
     arr = (nat.rg_layer * len(specs))()
-    for i, s in enumerate(specs):
-        arr[i].flags = ((nat.RG_LAYER_CENTERED
-                         if fmts is not None and fmts[i] & nat.RG_PACK_CENTERED else 0)
-                        | (nat.RG_LAYER_F16 if fmts is not None and fmts[i] & nat.RG_PACK_F16 else 0)
-                        | (nat.RG_LAYER_H2 if fmts is not None and fmts[i] & nat.RG_PACK_H2 else 0))
-        arr[i].w_packed = base + offs[i]
-        arr[i].norm_mu = nat.ptr(s.mu.detach()) if s.mu is not None else None
-        arr[i].norm_std = nat.ptr(s.std.detach()) if s.std is not None else None
-        arr[i].in_dim = s.in_dim
-        arr[i].out_dim = s.out_dim
-        arr[i].act = nat.ACT[s.act]
+    for i, sp in enumerate(specs):
+        _describe(arr[i], base + offs[i], sp.in_dim, sp.out_dim, sp, fmts[i] if fmts else 0)
     return arr
+
+
+@dataclass
+class PackedImage:
+    """One layer's packed image.  Its first pack and its rg_pack_linear_jobs entry (the
+    re-write in place) are two views of this one record."""
+    weight: torch.Tensor            # float32 source, held here: packing is asynchronous
+    bias: Optional[torch.Tensor]
+    wptr: int                       # weight.data_ptr() + 4 * col0
+    in_dim: int                     # of the image: a transposed image swaps the layer's
+    out_dim: int
+    fmt: int                        # format with its RG_PACK_* flags, RG_PACK_TRANSPOSE apart
+    transpose: bool
+    ld: int                         # row stride of the source (a column block); 0 = dense
+    packed: int                     # device address of the image
+
+    def pack(self, lib, stream):
+        fmt = self.fmt | (nat.RG_PACK_TRANSPOSE if self.transpose else 0)
+        if self.ld:
+            nat.check(lib.rg_pack_linear_ld(self.wptr, nat.ptr(self.bias), self.in_dim,
+                                            self.out_dim, fmt, self.ld, self.packed, stream),
+                      'rg_pack_linear_ld')
+        else:
+            nat.check(lib.rg_pack_linear(self.wptr, nat.ptr(self.bias), self.in_dim, self.out_dim,
+                                         fmt, self.packed, stream), 'rg_pack_linear')
+
+    def job(self) -> 'nat.rg_pack_job':
+        j = nat.rg_pack_job()
+        j.weight, j.bias, j.packed = self.wptr, nat.ptr(self.bias), self.packed
+        j.in_dim, j.out_dim, j.fmt = self.in_dim, self.out_dim, self.fmt
+        j.transpose, j.ld = int(self.transpose), self.ld
+        return j
+
+
+@dataclass
+class _Held:
+    gen: int        # PackedImages.gen when packed: older = stale
+    buf: torch.Tensor
+    images: List[PackedImage]
+    groups: list    # [(rg_layer array, layers, out_dim)]
+    in_place: bool  # rg_pack_linear_jobs writes it: RG_F32 / RG_PACK_F32_FAST, read where the
+                    # float32 parameters lie (no converted copy, no derived specs)
+
+
+class PackedImages:
+    """Every packed image made from one list of LayerSpecs on one device.
+
+    get(fmts, transpose, block) names an image set by what distinguishes it: the per-layer
+    formats (RG_PACK_* flags included), transposed or not, and optionally one column block
+    (layer, col0, width) of one layer (fmts then has that layer's format only).  The first
+    request packs it into a buffer of its own; later ones return the held descriptor arrays.
+
+    One validity state: the signature (data_ptr, _version) of every tensor of `sources` (the
+    specs, or the parameters they were derived from: their owner then replaces `specs` after a
+    refresh()).  refresh() compares it, invalidate() does not ask; either makes every held
+    image stale, and a stale image is packed again by its next request."""
+
+    def __init__(self, specs: List[LayerSpec], device, sources: Optional[List[LayerSpec]] = None):
+        self.specs = specs
+        self.sources = specs if sources is None else sources
+        self._tensors = [t for s in self.sources for t in (s.weight, s.bias, s.mu, s.std)
+                         if t is not None]
+        self.device = torch.device(device)
+        self.gen = 0
+        self.sig = self.signature()
+        self._held = {}
+
+    def signature(self):
+        return tuple([(t.data_ptr(), t._version) for t in self._tensors])
+
+    def refresh(self) -> bool:
+        """Whether the sources changed (every held image is stale then)."""
+        sig = self.signature()
+        if sig == self.sig:
+            return False
+        self.sig = sig
+        self.gen += 1
+        return True
+
+    def invalidate(self):
+        """The sources were written behind torch's version counters (FusedSGD)."""
+        self.sig = None
+        self.gen += 1
+
+    def held(self) -> list:
+        """Keys (fmts, transpose, block) of the images held and valid."""
+        return [k for k, e in self._held.items() if e.gen == self.gen]
+
+    def get(self, fmts: tuple, transpose: bool = False, block: Optional[tuple] = None) -> list:
+        """Descriptor groups [(rg_layer array, layers, out_dim)] of one image set: the chain in
+        groups of <= MAX_LAYERS layers; transposed or as a column block, every layer a group of
+        its own, a bare Linear (no bias, norm or activation)."""
+        key = (fmts, transpose, block)
+        e = self._held.get(key)
+        if e is None or e.gen != self.gen:
+            e = self._held[key] = self._pack(fmts, transpose, block, e)
+        return e.groups
+
+    def peek(self, fmts: tuple, transpose: bool = False, block: Optional[tuple] = None):
+        """get() without packing: None unless the set is held and valid."""
+        e = self._held.get((fmts, transpose, block))
+        return e.groups if e is not None and e.gen == self.gen else None
+
+    def _pack(self, fmts, transpose, block, old) -> _Held:
+        lib = nat.lib()
+        bare = transpose or block is not None
+        layers = ([(s, 0, s.in_dim) for s in self.specs] if block is None
+                  else [(self.specs[block[0]], block[1], block[2])])
+        images, tot = [], 0
+        for (s, col0, width), f in zip(layers, fmts):
+            w = s.weight.detach()
+            if block is None:
+                w = w.to(torch.float32).contiguous()
+            b = None if bare or s.bias is None else s.bias.detach().to(torch.float32).contiguous()
+            i, o = (s.out_dim, width) if transpose else (width, s.out_dim)
+            images.append(PackedImage(w, b, w.data_ptr() + 4 * col0, i, o, f, transpose,
+                                      0 if block is None else s.in_dim, tot))
+            tot += (lib.rg_packed_linear_bytes(i, o, f) + 255) // 256 * 256
+        buf = old.buf if old is not None and old.buf.numel() == tot else \
+            torch.empty(tot, dtype=torch.uint8, device=self.device)
+        st = nat.stream_ptr(self.device)
+        arr = (nat.rg_layer * len(images))()
+        for d, im, (s, _, _) in zip(arr, images, layers):
+            im.packed += buf.data_ptr()
+            im.pack(lib, st)
+            _describe(d, im.packed, im.in_dim, im.out_dim, None if bare else s, im.fmt)
+        step = 1 if bare else nat.MAX_LAYERS
+        groups = []
+        for g0 in range(0, len(images), step):
+            n = min(step, len(images) - g0)
+            grp = (nat.rg_layer * n).from_buffer(arr, g0 * ctypes.sizeof(nat.rg_layer))
+            groups.append((grp, n, images[g0 + n - 1].out_dim))
+        in_place = self.sources is self.specs and all(
+            im.fmt in (nat.RG_F32, nat.RG_PACK_F32_FAST)
+            and im.weight.data_ptr() == s.weight.data_ptr()
+            and (im.bias is None or im.bias.data_ptr() == s.bias.data_ptr())
+            for im, (s, _, _) in zip(images, layers))
+        return _Held(self.gen, buf, images, groups, in_place)
+
+    def jobs(self) -> Optional[list]:
+        """rg_pack_job entries that re-write every held, valid image in place, or None: the
+        generic float32 image is not packed (or stale), or some held image is not in_place."""
+        base = self._held.get(((nat.RG_F32,) * len(self.specs), False, None))
+        if base is None or base.gen != self.gen:
+            return None
+        out = []
+        for e in self._held.values():
+            if not e.in_place:
+                return None
+            if e.gen == self.gen:
+                out += [im.job() for im in e.images]
+        return out
 
 
 def _shape_refusal(rows, out, *ins) -> bool:
@@ -208,7 +353,7 @@ def _shape_refusal(rows, out, *ins) -> bool:
 
 
 class ChainPlan:
-    """Packed weights + launch descriptors of one or more rg_mlp_chain calls."""
+    """One or more rg_mlp_chain calls over the packed images of one chain."""
 
     def __init__(self, specs: List[LayerSpec], dtype: str, device):
         if not specs:
@@ -220,10 +365,26 @@ class ChainPlan:
         self.in_dim = specs[0].in_dim
         self.out_dim = specs[-1].out_dim
         self.use_fast = True   # try rg_mlp_chain_fast (bf16) / rg_mlp_chain_f32 (fp32) first
+        self.images = PackedImages(specs, device)
         self.pieces = None
         if any(s.frame_norm for s in specs):
             self._split_frame_norms()
             return
+        n = len(specs)
+
+        def chain_fmts(flag):   # the register-chain formats: layer 0 from memory
+            return tuple(centered_fmt(s, (nat.RG_PACK_FAST_CHAIN if i else nat.RG_PACK_FAST_IN)
+                                      | flag) for i, s in enumerate(specs))
+        # the generic chain kernel (any widths <= 512; fp16 in bf16's fragment layout with
+        # fp16 elements, RG_PACK_F16)
+        self.fmt_generic = ((nat.RG_BF16 | nat.RG_PACK_F16) if dtype == 'fp16' else self.dt,) * n
+        # 16-bit: also the register-resident 32x32x16 formats of rg_mlp_chain_fast
+        self.fmt_fast = (chain_fmts(_half_flag(dtype))
+                         if dtype in HALF and n <= nat.MAX_LAYERS else None)
+        # fp32, packed on first use: rg_mlp_chain_f32 (training chains never use it) and
+        # rg_mlp_chain_x3 under either term scheme
+        self.fmt_f32 = (nat.RG_PACK_F32_FAST,) * n
+        self.fmt_x3 = {'h2': chain_fmts(nat.RG_PACK_H2), 'b3': chain_fmts(nat.RG_PACK_X3)}
         self._pack()
 
     @property
@@ -234,7 +395,8 @@ class ChainPlan:
         """layer / group normalisation (common.py:223-253) normalise over a whole frame,
         which no fused chain can see: the chain is cut after every such layer.  Each piece
         is a ChainPlan whose last layer (when it carries a frame norm) is packed as a bare
-        Linear; rg_frame_norm then applies the norm + activation with per-frame stats."""
+        Linear; rg_frame_norm then applies the norm + activation with per-frame stats.  The
+        images are the pieces': this plan's own set stays empty."""
         if self.dtype != 'fp32':
             raise NotImplementedError('layer / group normalisation run in fp32 only')
         self.pieces = []
@@ -248,65 +410,46 @@ class ChainPlan:
                 cur.append(sp)
         if cur:
             self.pieces.append((ChainPlan(cur, self.dtype, self.device), None))
-        self.sig = self._signature()
-
-    def _signature(self):
-        sig = []
-        for s in self.specs:
-            for t in (s.weight, s.bias, s.mu, s.std):
-                if t is not None:
-                    sig.append((t.data_ptr(), t._version))
-        return tuple(sig)
-
-    def _pack_buffer(self, fmt_of_layer):
-        """Pack every layer (format fmt_of_layer(i)) into one device buffer; returns
-        (buffer, descriptor groups of <= MAX_LAYERS layers)."""
-        fmts = [fmt_of_layer(i) for i in range(len(self.specs))]
-        buf, offs = pack_specs(self.specs, fmts, self.device)
-        groups = []
-        for g0 in range(0, len(self.specs), nat.MAX_LAYERS):
-            grp = list(range(g0, min(g0 + nat.MAX_LAYERS, len(self.specs))))
-            arr = layer_array([self.specs[i] for i in grp], buf.data_ptr(), [offs[i] for i in grp],
-                              [fmts[i] for i in grp])
-            groups.append((arr, len(grp), self.specs[grp[-1]].out_dim))
-        return buf, groups
 
     def _pack(self):
+        """What is packed at once, at construction and after a change: the generic image and
+        the 16-bit register-chain one."""
         for s in self.specs:
             for t in (s.weight, s.bias, s.mu, s.std):
                 if t is not None:
                     _require_device(t, 'model parameter')
-        # the generic chain kernel (any widths <= 512; fp16 in bf16's fragment layout with
-        # fp16 elements, RG_PACK_F16)
-        self.buf, self.groups = self._pack_buffer(
-            lambda i: (nat.RG_BF16 | nat.RG_PACK_F16) if self.dtype == 'fp16' else self.dt)
-        # 16-bit: also the register-resident 32x32x16 formats of rg_mlp_chain_fast
-        self.fast = None
-        if self.dtype in HALF and len(self.specs) <= nat.MAX_LAYERS:
-            hf = _half_flag(self.dtype)
-            self.fast_buf, fg = self._pack_buffer(lambda i: centered_fmt(
-                self.specs[i], (nat.RG_PACK_FAST_IN if i == 0 else nat.RG_PACK_FAST_CHAIN) | hf))
-            self.fast = fg[0][0]
+        self.images.get(self.fmt_generic)
+        if self.fmt_fast is not None:
+            self.images.get(self.fmt_fast)
         self.fast_ok = {}   # in_mode -> bool (shape has a compiled fast kernel)
-        self._f32 = None    # RG_PACK_F32_FAST layer array, packed on first fp32 fast call
-        self._x3 = None     # RG_PACK_X3 layer array (rg_mlp_chain_x3), likewise
         self.x3_ok = {}     # in_mode -> bool (shape has a compiled x3 kernel)
-        self.sig = self._signature()
 
     def refresh(self):
         if self.pieces is not None:
             for p, _ in self.pieces:
                 p.refresh()
-            return
-        if self._signature() != self.sig:
+        elif self.images.refresh():
             self._pack()
 
     def invalidate(self):
         """Parameters were written behind torch's version counters (FusedSGD)."""
-        self.sig = None
+        self.images.invalidate()
         if self.pieces is not None:
             for p, _ in self.pieces:
                 p.invalidate()
+
+    def x3_fmts(self) -> tuple:
+        """Formats of the rg_mlp_chain_x3 image under the current engine.X3_TERMS."""
+        try:
+            return self.fmt_x3[X3_TERMS]
+        except KeyError:
+            raise ValueError(f"engine.X3_TERMS must be 'h2' or 'b3', not {X3_TERMS!r}") from None
+
+    @property
+    def _x3(self):
+        """The rg_mlp_chain_x3 descriptors held under the current engine.X3_TERMS, or None."""
+        groups = self.images.peek(self.x3_fmts())
+        return groups[0][0] if groups else None
 
     def _call_pieces(self, rows, out, in0, w0, mode, in1, w1, in2, w2, idx0, idx1, residual,
                      rows_dev, segs):
@@ -350,27 +493,6 @@ class ChainPlan:
             cur = (dst, plan.out_dim, nat.IN_DENSE, None, 0, None, 0, None, None)
         return out
 
-    def _x3_layers(self):
-        """The chain packed RG_PACK_X3 (layer 0 FAST_IN, later FAST_CHAIN) for
-        rg_mlp_chain_x3 (lazily)."""
-        if self._x3 is None or self._x3_terms != X3_TERMS:
-            if X3_TERMS not in ('h2', 'b3'):
-                raise ValueError(f"engine.X3_TERMS must be 'h2' or 'b3', not {X3_TERMS!r}")
-            X3 = nat.RG_PACK_H2 if X3_TERMS == 'h2' else nat.RG_PACK_X3
-            self._x3_terms = X3_TERMS
-            self._x3buf, groups = self._pack_buffer(lambda i: centered_fmt(
-                self.specs[i], (nat.RG_PACK_FAST_IN if i == 0 else nat.RG_PACK_FAST_CHAIN) | X3))
-            self._x3 = groups[0][0]
-        return self._x3
-
-    def _f32_layers(self):
-        """The chain packed RG_PACK_F32_FAST for rg_mlp_chain_f32 (lazily: training chains
-        never use it)."""
-        if self._f32 is None:
-            self._f32buf, groups = self._pack_buffer(lambda i: nat.RG_PACK_F32_FAST)
-            self._f32 = groups[0][0]
-        return self._f32
-
     def __call__(self, rows: int, out: torch.Tensor, in0: torch.Tensor, w0: int,
                  mode: int = nat.IN_DENSE, in1=None, w1: int = 0, in2=None, w2: int = 0,
                  idx0=None, idx1=None, residual=None, rows_dev=None, segs=None):
@@ -379,12 +501,13 @@ class ChainPlan:
                                      residual, rows_dev, segs)
         lib = nat.lib()
         st = nat.stream_ptr(self.device)
+        img = self.images.get
         keep = lambda: _shape_refusal(rows, out, in0, in1, in2, residual)  # noqa: E731
         f32_fast = (self.use_fast and self.dt == nat.RG_F32 and mode in (nat.IN_DENSE, nat.IN_PAIRADD)
                     and residual is None and in0.dtype == torch.float32
                     and out.dtype == torch.float32 and len(self.specs) <= nat.MAX_LAYERS)
         if f32_fast and F32_ARITH == 'x3' and self.x3_ok.get(mode, True):
-            rc = lib.rg_mlp_chain_x3(self._x3_layers(), len(self.specs), int(rows),
+            rc = lib.rg_mlp_chain_x3(img(self.x3_fmts())[0][0], len(self.specs), int(rows),
                                      nat.ptr(rows_dev), mode, in0.data_ptr(), in0.stride(0), w0,
                                      nat.ptr(idx0), nat.ptr(idx1), out.data_ptr(), out.stride(0), st)
             if rc == 0:
@@ -395,7 +518,7 @@ class ChainPlan:
             if keep():
                 self.x3_ok[mode] = False
         if f32_fast and self.fast_ok.get(mode, True):
-            rc = lib.rg_mlp_chain_f32(self._f32_layers(), len(self.specs), int(rows),
+            rc = lib.rg_mlp_chain_f32(img(self.fmt_f32)[0][0], len(self.specs), int(rows),
                                       nat.ptr(rows_dev), mode, in0.data_ptr(), in0.stride(0), w0,
                                       nat.ptr(idx0), nat.ptr(idx1), out.data_ptr(), out.stride(0),
                                       st)
@@ -406,9 +529,10 @@ class ChainPlan:
                 nat.check(rc, 'rg_mlp_chain_f32')
             if keep():
                 self.fast_ok[mode] = False
-        if self.use_fast and self.fast is not None and self.fast_ok.get(mode, True):
+        if self.use_fast and self.fmt_fast is not None and self.fast_ok.get(mode, True):
             rc = lib.rg_mlp_chain_fast(
-                self.fast, len(self.specs), int(rows), nat.ptr(rows_dev), mode, _dt_code(in0),
+                img(self.fmt_fast)[0][0], len(self.specs), int(rows), nat.ptr(rows_dev), mode,
+                _dt_code(in0),
                 in0.data_ptr(), in0.stride(0), w0,
                 nat.ptr(in1), in1.stride(0) if in1 is not None else 0, w1,
                 nat.ptr(in2), in2.stride(0) if in2 is not None else 0, w2,
@@ -423,14 +547,10 @@ class ChainPlan:
                 nat.check(rc, 'rg_mlp_chain_fast')
             if keep():
                 self.fast_ok[mode] = False
-        if self.groups is None:
-            raise NotImplementedError(
-                f'fp16 chains run on the register-resident fast kernels only, which have no '
-                f'instantiation for this chain (widths {[s.out_dim for s in self.specs]}, input '
-                f'mode {mode}); use fp32 or bf16')
         cur_in, cur_w, cur_mode = in0, w0, mode
-        for gi, (arr, n, gout) in enumerate(self.groups):
-            last = gi == len(self.groups) - 1
+        groups = img(self.fmt_generic)
+        for gi, (arr, n, gout) in enumerate(groups):
+            last = gi == len(groups) - 1
             dst = out if last else torch.empty((out.shape[0], gout), dtype=self.tdtype,
                                                device=self.device)
             res = residual if last else None
@@ -769,12 +889,13 @@ class ConvPlan:
         self.fused_ok = None
         self.use_fused = True   # bf16: one rg_conv_layer_fused launch per layer
         self.f32_arith = F32_ARITH if dtype == 'fp32' else None
+        self.images = None      # the fused layer kernel's image set (_pack_fused)
         self._pack_fused()
 
-    def _pack_fused_f32(self):
+    def _fused_specs_f32(self):
         """fp32: rg_conv_layer_f32's four RG_PACK_F32_FAST layers -- the per-node
         projection [W_xi; W_xj] (+ [b; 0]), W_e (msg0's edge columns, with msg0's norm and
-        activation), msg1, upd."""
+        activation), msg1, upd -- or rg_conv_layer_x3's five."""
         m0, m1 = self.msg.specs
         u = self.upd.specs[0]
         C = self.c_out
@@ -784,87 +905,73 @@ class ConvPlan:
         # channel-normalised + LeakyReLU); any other block runs the unfused chains
         if not (C == 64 and W.shape == (128, 3 * C) and m1.weight.shape == (C, 128)
                 and u.weight.shape == (C, 2 * C)):
-            return
+            return None
         if any(sp.mu is None or sp.act != 'leakyrelu' for sp in (m0, m1, u)):
-            return
+            return None
         b = (m0.bias.detach().to(torch.float32) if m0.bias is not None
              else torch.zeros(W.shape[0], dtype=torch.float32, device=W.device))
-        w_pq = torch.cat((W[:, :C], W[:, C:2 * C]), 0).contiguous()
-        b_pq = torch.cat((b, torch.zeros_like(b)), 0).contiguous()
-        pq = LayerSpec(w_pq, b_pq, None, None, 'none')
-        we = LayerSpec(W[:, 2 * C:].contiguous(), None, m0.mu, m0.std, m0.act)
-        specs = [pq, we, m1, u]
-        if self.f32_arith == 'x3':
-            X3, CEN = nat.RG_PACK_X3, nat.RG_PACK_CENTERED
-            # normalised layers packed zero-mean over their outputs (the kernel then skips
-            # the mean pass): msg0 is centred here as a whole -- its x_i, x_j and edge
-            # columns (P, Q, W_e) and its bias -- and msg1 / upd by the packer
-            Wc = W - W.mean(0, keepdim=True)
-            bc = b - b.mean()
-            pq = LayerSpec(torch.cat((Wc[:, :C], Wc[:, C:2 * C]), 0).contiguous(),
-                           torch.cat((bc, torch.zeros_like(bc)), 0).contiguous(), None, None, 'none')
-            we = LayerSpec(Wc[:, 2 * C:].contiguous(), None, m0.mu, m0.std, m0.act)
-            w_pq, b_pq = pq.weight, pq.bias
-            # [0] W_e, [1] msg1, [2] upd (cat(x, agg) read from memory), [3] P | Q from
-            # memory (first layer), [4] P | Q from the previous layer's registers
-            specs = [we, m1, u, pq, pq]
-            fmts = [nat.RG_PACK_FAST_IN | X3, nat.RG_PACK_FAST_CHAIN | X3 | CEN,
-                    nat.RG_PACK_FAST_IN | X3 | CEN, nat.RG_PACK_FAST_IN | X3,
-                    nat.RG_PACK_FAST_CHAIN | X3]
-        else:
-            fmts = [nat.RG_PACK_F32_FAST] * 4
-        try:
-            self.fused_buf, offs = pack_specs(specs, fmts, self.device)
-        except RuntimeError:
-            return
-        self._fused_keep = (w_pq, b_pq, we.weight)   # packing is async: keep the sources
-        base = self.fused_buf.data_ptr()
-        if self.f32_arith == 'x3':
-            self.fused_layers = layer_array(specs[:3], base, offs[:3], fmts[:3])
-            self.fused_layers[0].flags = nat.RG_LAYER_CENTERED   # centred on the host
-            self.x3_pq_in = layer_array(specs[3:4], base, offs[3:4], fmts[3:4])
-            self.x3_pq_chain = layer_array(specs[4:5], base, offs[4:5], fmts[4:5])
-            self._ws = {}
-            self.x3_pq = None   # projections of a standalone run_fused call
-        else:
-            self.fused_layers = layer_array(specs, base, offs, fmts)
-            self._ws = {}
-        self.fused = True
-        self.fused_sig = self._sig()
+        if self.f32_arith != 'x3':
+            pq = LayerSpec(torch.cat((W[:, :C], W[:, C:2 * C]), 0).contiguous(),
+                           torch.cat((b, torch.zeros_like(b)), 0).contiguous(), None, None, 'none')
+            we = LayerSpec(W[:, 2 * C:].contiguous(), None, m0.mu, m0.std, m0.act)
+            return [pq, we, m1, u], (nat.RG_PACK_F32_FAST,) * 4
+        X3, CEN = nat.RG_PACK_X3, nat.RG_PACK_CENTERED
+        # normalised layers packed zero-mean over their outputs (the kernel then skips
+        # the mean pass): msg0 is centred here as a whole -- its x_i, x_j and edge
+        # columns (P, Q, W_e) and its bias -- and msg1 / upd by the packer
+        Wc = W - W.mean(0, keepdim=True)
+        bc = b - b.mean()
+        pq = LayerSpec(torch.cat((Wc[:, :C], Wc[:, C:2 * C]), 0).contiguous(),
+                       torch.cat((bc, torch.zeros_like(bc)), 0).contiguous(), None, None, 'none')
+        we = LayerSpec(Wc[:, 2 * C:].contiguous(), None, m0.mu, m0.std, m0.act, centered=True)
+        # [0] W_e, [1] msg1, [2] upd (cat(x, agg) read from memory), [3] P | Q from
+        # memory (first layer), [4] P | Q from the previous layer's registers
+        return [we, m1, u, pq, pq], (nat.RG_PACK_FAST_IN | X3, nat.RG_PACK_FAST_CHAIN | X3 | CEN,
+                                     nat.RG_PACK_FAST_IN | X3 | CEN, nat.RG_PACK_FAST_IN | X3,
+                                     nat.RG_PACK_FAST_CHAIN | X3)
+
+    def _fused_specs(self):
+        """(specs, formats) of the fused layer kernel's image set when the shapes fit -- 16-bit:
+        rg_conv_layer_fused's msg0, msg1, upd; fp32: _fused_specs_f32 -- else None."""
+        if self.res is not None or self.aggr == 'max':
+            return None
+        if any(c.has_frame_norm for c in self.chains()):
+            return None
+        if len(self.msg.specs) != 2 or len(self.upd.specs) != 1:
+            return None
+        if self.dtype == 'fp32':
+            return self._fused_specs_f32()
+        if self.dtype not in HALF:
+            return None
+        specs = self.msg.specs + self.upd.specs
+        hf = _half_flag(self.dtype)
+        return specs, tuple(centered_fmt(sp, f | hf) for sp, f in zip(
+            specs, (nat.RG_PACK_FAST_IN, nat.RG_PACK_FAST_CHAIN, nat.RG_PACK_FAST_UPD)))
 
     def _pack_fused(self):
-        """bf16: the fused layer kernel (rg_conv_layer_fused) when the shapes fit;
-        fp32: rg_conv_layer_f32."""
+        """The fused set, a PackedImages over specs derived here from the message and update
+        chains' parameters, which its validity follows: at construction, and derived and
+        packed again after a change (refresh)."""
         self.fused = None
-        if self.res is not None or self.aggr == 'max':
+        derived = self._fused_specs()
+        if derived is None:
             return
-        if any(c.has_frame_norm for c in self.chains()):
-            return
-        if len(self.msg.specs) != 2 or len(self.upd.specs) != 1:
-            return
-        if self.dtype == 'fp32':
-            return self._pack_fused_f32()
-        if self.dtype not in HALF:
-            return
-        specs = self.msg.specs + self.upd.specs
-        if len(self.msg.specs) != 2 or len(self.upd.specs) != 1:
-            return
-        hf = _half_flag(self.dtype)
-        fmts = [centered_fmt(sp, f | hf) for sp, f in
-                zip(specs, [nat.RG_PACK_FAST_IN, nat.RG_PACK_FAST_CHAIN, nat.RG_PACK_FAST_UPD])]
+        specs, self.fused_fmts = derived
+        if self.images is None:
+            self.images = PackedImages(specs, self.device, self.msg.specs + self.upd.specs)
+        self.images.specs = specs
         try:
-            self.fused_buf, offs = pack_specs(specs, fmts, self.device)
+            self.images.get(self.fused_fmts)
         except RuntimeError:
             return
-        base = self.fused_buf.data_ptr()
-        self.fused_msg = layer_array(specs[:2], base, offs[:2], fmts[:2])
-        self.fused_upd = layer_array(specs[2:], base, offs[2:], fmts[2:])
         self._ws = {}
+        self.x3_pq = None   # fp32 x3: projections of a standalone run_fused call
         self.fused = True
-        self.fused_sig = self._sig()
 
-    def _sig(self):
-        return tuple(c._signature() for c in self.chains())
+    def _layers(self, first: int = 0):
+        """The fused set's descriptors from layer `first` on."""
+        arr = self.images.get(self.fused_fmts)[0][0]
+        return arr if first == 0 else ctypes.byref(arr[first])
 
     def workspace(self, need: int, stream: int) -> torch.Tensor:
         """The fused conv workspace of one HIP stream (zeroed when allocated: its leading
@@ -882,13 +989,14 @@ class ConvPlan:
     def refresh(self):
         for c in self.chains():
             c.refresh()
-        if self.fused and self._sig() != self.fused_sig:
+        if self.fused and self.images.refresh():
             self._pack_fused()
 
     def invalidate(self):
         for c in self.chains():
             c.invalidate()
-        self.fused_sig = None
+        if self.images is not None:
+            self.images.invalidate()
 
     @property
     def x3(self) -> bool:
@@ -901,7 +1009,7 @@ class ConvPlan:
     def project_x3(self, x, pq) -> bool:
         """P | Q of the first x3 layer (rg_conv_proj_x3); False when the kernel does not
         take this layer (the caller then runs the layer unfused)."""
-        rc = nat.lib().rg_conv_proj_x3(self.x3_pq_in, x.data_ptr(), x.stride(0), x.shape[0],
+        rc = nat.lib().rg_conv_proj_x3(self._layers(3), x.data_ptr(), x.stride(0), x.shape[0],
                                        pq.data_ptr(), nat.stream_ptr(x.device))
         if rc == nat.RG_ERR_UNSUPPORTED:
             self.fused_ok = False
@@ -916,7 +1024,7 @@ class ConvPlan:
         st = nat.stream_ptr(x.device)
         ws = self.workspace(lib.rg_conv_layer_x3_workspace_size(g.n_nodes), st)
         tbl = g.conv_x3_blocks()
-        args = (self.fused_layers, nxt.x3_pq_chain if nxt is not None else None,
+        args = (self._layers(), nxt._layers(4) if nxt is not None else None,
                 nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0), e.data_ptr(), e.stride(0),
                 pq.data_ptr(), g.seg_ptr.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(), g.n_nodes,
                 x_out.data_ptr(), x_out.stride(0), nat.ptr(pq_out))
@@ -953,7 +1061,7 @@ class ConvPlan:
             st = nat.stream_ptr(x.device)
             ws = self.workspace(lib.rg_conv_layer_f32_workspace_size(g.n_nodes), st)
             rc = lib.rg_conv_layer_f32(
-                self.fused_layers, nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0), e.data_ptr(),
+                self._layers(), nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0), e.data_ptr(),
                 e.stride(0), g.seg_ptr.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(), g.n_nodes,
                 x_out.data_ptr(), x_out.stride(0), ws.data_ptr(), ws.numel(), st)
             if rc == nat.RG_ERR_UNSUPPORTED:
@@ -967,14 +1075,14 @@ class ConvPlan:
         wn = g.conv_waves()
         if wn is not None:
             rc = lib.rg_conv_layer_fused_waves(
-                self.fused_msg, self.fused_upd, nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0),
+                self._layers(), self._layers(2), nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0),
                 e.data_ptr(), e.stride(0), g.seg_ptr.data_ptr(), g.src.data_ptr(),
                 g.dst.data_ptr(), g.n_nodes, x_out.data_ptr(), x_out.stride(0), wn.data_ptr(),
                 wn.numel() - 1, ws.data_ptr(), st)
         else:
             tbl, nb = g.conv_blocks()
             rc = lib.rg_conv_layer_fused_blocks(
-                self.fused_msg, self.fused_upd, nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0),
+                self._layers(), self._layers(2), nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0),
                 e.data_ptr(), e.stride(0), g.seg_ptr.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(),
                 g.n_nodes, x_out.data_ptr(), x_out.stride(0), nat.ptr(tbl), nat.ptr(nb),
                 ws.data_ptr(), st)
@@ -1003,12 +1111,12 @@ class ModelPlans:
         self.link_pair = mk(list(pl.stem) + [pl.pred_cls.head[0], pl.pred_cls.head[1]])
         self.cls_stem = mk(list(pc.stem)) if len(pc.stem) else None
         self.cls_head = mk([pc.pred_cls.head[0], pc.pred_cls.head[1]])
-        # layer / group normalisation anywhere: chains need each frame's row ranges
-        self.frame_norm = any(c.has_frame_norm for c in self.chains())
         # fp32 link head: the pair chain's first Linear is applied per NODE (t = W0 s, a bare
         # last layer after the compute_edge stem) and the pairs start from t_i + t_j + b0
         # (RG_IN_PAIRPRE, link_pairs_pre); None: the pairs run the whole chain (RG_IN_PAIRADD)
         self.link_pre = None
+        # layer / group normalisation anywhere: chains need each frame's row ranges
+        self.frame_norm = any(c.has_frame_norm for c in self.chains())
         first = self.link_pair.specs[0]
         if (dtype == 'fp32' and LINK_PRE and not self.frame_norm and first.mu is not None
                 and len(self.link_pair.specs) > 1):
@@ -1018,14 +1126,13 @@ class ModelPlans:
             stem = list(self.link_node.specs) if self.link_node is not None else []
             self.link_pre = ChainPlan(stem + [bare], dtype, device)
 
+    def _heads(self):
+        return [c for c in (self.node_enc, self.edge_enc, self.node_head, self.offset_head,
+                            self.link_pair, self.cls_head, self.link_node, self.cls_stem,
+                            self.link_pre) if c is not None]
+
     def chains(self):
-        out = [self.node_enc, self.edge_enc, self.node_head, self.offset_head, self.link_pair,
-               self.cls_head]
-        out += [c for c in (self.link_node, self.cls_stem, getattr(self, 'link_pre', None))
-                if c is not None]
-        for cv in self.convs:
-            out += cv.chains()
-        return out
+        return self._heads() + [c for cv in self.convs for c in cv.chains()]
 
     def link_pairs_pre(self, N, x, C, ucap, link, g) -> bool:
         """The link head through RG_IN_PAIRPRE: t = [stem ->] W0 x per node, then the pair
@@ -1040,7 +1147,7 @@ class ModelPlans:
             lp.x3_ok['pre'] = False
             return False
         lib = nat.lib()
-        rc = lib.rg_mlp_chain_x3(pair._x3_layers(), len(pair.specs), int(ucap),
+        rc = lib.rg_mlp_chain_x3(pair.images.get(pair.x3_fmts())[0][0], len(pair.specs), int(ucap),
                                  nat.ptr(g.n_pairs_dev), nat.IN_PAIRPRE, t.data_ptr(), t.stride(0),
                                  lp.out_dim, g.pair_src.data_ptr(), g.pair_dst.data_ptr(),
                                  link.data_ptr(), link.stride(0), nat.stream_ptr(x.device))
@@ -1052,20 +1159,12 @@ class ModelPlans:
         return True
 
     def refresh(self):
-        for c in (self.node_enc, self.edge_enc, self.node_head, self.offset_head, self.link_pair,
-                  self.cls_head, self.link_node, self.cls_stem, self.link_pre):
-            if c is not None:
-                c.refresh()
-        for cv in self.convs:
-            cv.refresh()
+        for p in self._heads() + self.convs:
+            p.refresh()
 
     def invalidate(self):
-        for c in (self.node_enc, self.edge_enc, self.node_head, self.offset_head, self.link_pair,
-                  self.cls_head, self.link_node, self.cls_stem, self.link_pre):
-            if c is not None:
-                c.invalidate()
-        for cv in self.convs:
-            cv.invalidate()
+        for p in self._heads() + self.convs:
+            p.invalidate()
 
 
 @dataclass

@@ -59,6 +59,8 @@ GATHERED_DMSG = True
 # dX = dZ W fused with the previous ffn_block's norm backward (rg_dx_norm_backward): dA never
 # written; the row sums in the chain layout's order (not rg_ffn_backward's)
 DX_NORM_FUSED = True
+# formats of the backward's transposed images, one layer's (TrainChain._wt)
+_DX_FMTS = ((nat.RG_F32,), (nat.RG_PACK_F32_FAST,))
 
 
 def _f32(t: torch.Tensor) -> torch.Tensor:
@@ -117,11 +119,9 @@ class TrainChain:
         self.plan = ChainPlan(packed, 'fp32', device)
         self._fast_ok = {}   # input mode -> the register-resident tape kernel took the chain
         self._dx_ok = {}     # layer -> the register-resident kernel took its dX = dZ W
-        self._sub = {}       # (layer, col0, width) -> column-block images for dX (_block_images)
-        self._subsig = None
+        self._wt_memo = {}   # layer or (layer, col0, width) -> (images.gen, _wt's pair)
         self.device = torch.device(device)
         self.ws = ws
-        self._tsig = None
         self.in_dim = self.plan.in_dim
         self.out_dim = self.plan.out_dim
 
@@ -129,136 +129,36 @@ class TrainChain:
         self.plan.refresh()
 
     def invalidate(self):
-        self.plan.sig = None
-        self._tsig = None
-        self._subsig = None
+        self.plan.invalidate()
 
     def pack_jobs(self):
-        """rg_pack_job entries that re-write every packed image of this chain in place (the
-        generic and register-resident f32 images and their transposes), or None when the
-        chain is not fully packed yet or packs something else (frame-norm pieces)."""
-        p = self.plan
-        if p.pieces is not None or p.sig is None or p.dt != nat.RG_F32:
-            return None
-        jobs = []
+        """rg_pack_job entries that re-write every packed image of this chain in place, or
+        None (engine.PackedImages.jobs)."""
+        return self.plan.images.jobs()
 
-        def job(w, b, dst, i, o, fmt, tr):
-            j = nat.rg_pack_job()
-            j.weight, j.bias, j.packed = w.data_ptr(), nat.ptr(b), dst
-            j.in_dim, j.out_dim, j.fmt, j.transpose = i, o, fmt, tr
-            jobs.append(j)
-
-        for g0, (arr, n, _) in zip(range(0, len(p.specs), nat.MAX_LAYERS), p.groups):
-            for i in range(n):
-                s = p.specs[g0 + i]
-                job(s.weight.detach(), None if s.bias is None else s.bias.detach(), arr[i].w_packed,
-                    s.in_dim, s.out_dim, nat.RG_F32, 0)
-        if p._f32 is not None:
-            for i, s in enumerate(p.specs):
-                job(s.weight.detach(), None if s.bias is None else s.bias.detach(),
-                    p._f32[i].w_packed, s.in_dim, s.out_dim, nat.RG_PACK_F32_FAST, 0)
-        if self._tsig is not None and self._tsig == p.sig:
-            for s, pair in zip(self.specs, self._tarr):
-                for fmt, arr in zip((nat.RG_F32, nat.RG_PACK_F32_FAST), pair):
-                    job(s.weight.detach(), None, arr[0].w_packed, s.out_dim, s.in_dim, fmt, 1)
-        else:
-            self._tsig = None   # transposes not packed yet: packed on first use
-        if self._subsig is not None and self._subsig == p.sig:
-            for (l, c0, wd), pair in self._sub.items():
-                s = self.specs[l]
-                for fmt, arr in zip((nat.RG_F32, nat.RG_PACK_F32_FAST), pair):
-                    job(s.weight.detach(), None, arr[0].w_packed, s.out_dim, wd, fmt, 1)
-                    jobs[-1].weight = s.weight.data_ptr() + 4 * c0
-                    jobs[-1].ld = s.in_dim
-        else:
-            self._subsig = None
-        return jobs
-
-    def _transposed(self):
-        """W^T of every layer (no bias / norm / activation) for the data GEMM of the
-        backward, dX = dZ W: per layer (generic RG_F32 image, register-resident
-        RG_PACK_F32_FAST image), both packed transposed."""
-        sig = self.plan.sig
-        if self._tsig == sig:
-            return self._tarr
-        lib = nat.lib()
-        st = nat.stream_ptr(self.device)
-        fmts = (nat.RG_F32, nat.RG_PACK_F32_FAST)
-        offs, tot = [], 0
-        for s in self.specs:
-            o = []
-            for f in fmts:
-                o.append(tot)
-                tot += (lib.rg_packed_linear_bytes(s.out_dim, s.in_dim, f) + 255) // 256 * 256
-            offs.append(o)
-        self._tbuf = torch.empty(tot, dtype=torch.uint8, device=self.device)
-        self._tarr = []
-        for s, o in zip(self.specs, offs):
-            w = s.weight.detach()
-            pair = []
-            for f, off in zip(fmts, o):
-                nat.check(lib.rg_pack_linear(w.data_ptr(), None, s.out_dim, s.in_dim,
-                                             f | nat.RG_PACK_TRANSPOSE, self._tbuf.data_ptr() + off,
-                                             st), 'rg_pack_linear')
-                arr = (nat.rg_layer * 1)()
-                arr[0].w_packed = self._tbuf.data_ptr() + off
-                arr[0].in_dim = s.out_dim
-                arr[0].out_dim = s.in_dim
-                arr[0].act = nat.ACT['none']
-                pair.append(arr)
-            self._tarr.append(tuple(pair))
-        self._tsig = sig
-        return self._tarr
-
-    def _block_images(self, l: int, col0: int, width: int):
-        """Images of the column block W_l[:, col0:col0 + width] for the data GEMM
-        dX_block = dZ W_l[:, col0:col0 + width] (generic RG_F32 and register-resident
-        RG_PACK_F32_FAST, packed transposed straight from the block: rg_pack_linear_ld, row
-        stride in_dim), re-written in place with the other images after an optimizer step
-        (pack_jobs)."""
-        sig = self.plan.sig
-        key = (l, col0, width)
-        if self._subsig != sig:
-            self._sub_packed = {}
-            self._subsig = sig
-        if key in self._sub and key in self._sub_packed:
-            return self._sub[key]
-        lib = nat.lib()
-        st = nat.stream_ptr(self.device)
-        s = self.specs[l]
-        w = s.weight.detach()
-        arrs = []
-        for f in (nat.RG_F32, nat.RG_PACK_F32_FAST):
-            bkey = ('blk', id(self), key, f)
-            buf = self.ws.bufs.get(bkey)
-            if buf is None:
-                buf = torch.empty(lib.rg_packed_linear_bytes(s.out_dim, width, f),
-                                  dtype=torch.uint8, device=self.device)
-                self.ws.bufs[bkey] = buf
-            nat.check(lib.rg_pack_linear_ld(w.data_ptr() + 4 * col0, None, s.out_dim, width,
-                                            f | nat.RG_PACK_TRANSPOSE, s.in_dim, buf.data_ptr(),
-                                            st), 'rg_pack_linear_ld')
-            arr = (nat.rg_layer * 1)()
-            arr[0].w_packed = buf.data_ptr()
-            arr[0].in_dim = s.out_dim
-            arr[0].out_dim = width
-            arr[0].act = nat.ACT['none']
-            arrs.append(arr)
-        self._sub[key] = tuple(arrs)
-        self._sub_packed[key] = True
-        return self._sub[key]
+    def _wt(self, l: int, block=None):
+        """(generic RG_F32, register-resident RG_PACK_F32_FAST) images of W_l^T, a bare Linear,
+        for the backward's data GEMM dX = dZ W_l; block = (col0, width): of the column block
+        W_l[:, col0:col0 + width] alone.  Both are requested, so both are re-written in place
+        with the chain's other images; the pair is remembered while the images stay valid."""
+        im = self.plan.images
+        key = l if block is None else (l,) + tuple(block)
+        memo = self._wt_memo.get(key)
+        if memo is None or memo[0] != im.gen:
+            if block is None:
+                pair = tuple(im.get(f * len(self.specs), True)[l][0] for f in _DX_FMTS)
+            else:
+                pair = tuple(im.get(f, True, key)[0][0] for f in _DX_FMTS)
+            memo = self._wt_memo[key] = (im.gen, pair)
+        return memo[1]
 
     def _dx(self, l: int, rows: int, dZ, out, res, block=None):
         """out = dZ W_l (+ res): the register-resident f32 kernel where it has the shape,
         else the generic chain kernel.  block = (col0, width): dZ W_l[:, col0:col0 + width]."""
         lib = nat.lib()
         st = nat.stream_ptr(self.device)
-        if block is None:
-            gen, fast = self._transposed()[l]
-            okey = l
-        else:
-            gen, fast = self._block_images(l, *block)
-            okey = (l,) + tuple(block)
+        gen, fast = self._wt(l, block)
+        okey = l if block is None else (l,) + tuple(block)
         if TAPE_F32_FAST and DX_F32_FAST and self._dx_ok.get(okey, True):
             rc = lib.rg_mlp_chain_f32_ex(fast, 1, rows, None, nat.IN_DENSE, dZ.data_ptr(),
                                          dZ.stride(0), dZ.shape[1], None, 0, 0, None, 0, 0, None,
@@ -304,7 +204,7 @@ class TrainChain:
         self.plan.refresh()
         lib = nat.lib()
         dev = self.device
-        arr0, n, _ = self.plan.groups[0]
+        arr0, n, _ = self.plan.images.get(self.plan.fmt_generic)[0]
         z, a = [], []
         for i in range(n):
             zi = torch.empty((max(rows, 1), self.specs[i].out_dim), dtype=torch.float32, device=dev)
@@ -317,7 +217,7 @@ class TrainChain:
             # products on v_mfma_f32_32x32x2_f32): one launch, activations in registers.  The
             # last layer's activation is not taped (the backward reads a[l - 1] only): the
             # chain output stands for it when there is no residual
-            src = self.plan._f32_layers()
+            src = self.plan.images.get(self.plan.fmt_f32)[0][0]
             arr = (nat.rg_layer * n)()
             for i in range(n):
                 ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(src[i]), ctypes.sizeof(nat.rg_layer))
@@ -497,7 +397,7 @@ class TrainChain:
         if not self._dx_ok.get(key, True):
             return False
         lib = nat.lib()
-        _, fast = self._transposed()[l]
+        _, fast = self._wt(l)
         wsz = lib.rg_dx_norm_backward_workspace_size(rows)
         ws = self.ws.get('dxnb', wsz)
         rc = lib.rg_dx_norm_backward(
