@@ -21,6 +21,7 @@
 //    persistent workgroup; larger chains (the 7 -> 256 -> 128 -> 128 -> 64 edge encoder is
 //    232 KiB of f32 weights) read the remaining layers' fragments from global memory
 //    (L2-resident, prefetched several k-steps ahead).
+#include "pack_layout.h"
 #include "rg_common.h"
 
 namespace rg {
@@ -32,10 +33,6 @@ static constexpr int FT = 256;            // 4 waves, one per SIMD
 #define RG_CF32_DIVR 1  // the tape's channel-norm divides as reciprocal + one correction (0: __fdiv_rn)
 #endif
 
-// bytes of one RG_PACK_F32_FAST layer (fragments + accumulator-order bias)
-__host__ __device__ constexpr int fbytes(int K, int N) {
-  return (N / 32) * ((K + 7) / 8) * 1024 + N * 4;
-}
 __host__ __device__ constexpr int falign(int b) { return (b + 15) & ~15; }
 
 struct Layer {
@@ -339,7 +336,8 @@ template <int SPEC, int LI, int K> struct LdsOff<SPEC, LI, K> {
   static constexpr int total() { return 0; }
 };
 template <int SPEC, int LI, int K, int N, int... Rest> struct LdsOff<SPEC, LI, K, N, Rest...> {
-  static constexpr int mine() { return spec_glob(SPEC, LI) ? 0 : falign(fbytes(K, N)); }
+  static_assert(N % 32 == 0, "N: the layer's width padded to whole 32-row M-tiles");
+  static constexpr int mine() { return spec_glob(SPEC, LI) ? 0 : falign(f32_fast_bytes(K, N)); }
   static constexpr int get(int l) { return l == LI ? 0 : mine() + LdsOff<SPEC, LI + 1, N, Rest...>::get(l); }
   static constexpr int total() { return mine() + LdsOff<SPEC, LI + 1, N, Rest...>::total(); }
 };
@@ -538,7 +536,7 @@ __global__ __launch_bounds__(NT) void chain_f32_kernel(Args a) {
     for (int l = 0; l < NL; ++l) {
       if (!spec_glob(SPEC, l)) {
         const int K = l == 0 ? K0 : Ks[l - 1];
-        stage_lds<NT>(lds + Off::get(l), a.L[l].src, fbytes(K, Ks[l]));
+        stage_lds<NT>(lds + Off::get(l), a.L[l].src, f32_fast_bytes(K, Ks[l]));
       }
     }
   }
@@ -773,7 +771,7 @@ __global__ __launch_bounds__(FT, dxnb_wps<K0>()) void dx_norm_bwd_kernel(Args a,
   __shared__ double red[FT / 64][2];
   constexpr int S40 = K0 / 8, MT = N / 32, C = N;
   static_assert(K0 % 8 == 0 && N % 32 == 0, "dx_norm_bwd widths");
-  stage_lds<FT>(lds, a.L[0].src, fbytes(K0, N));
+  stage_lds<FT>(lds, a.L[0].src, f32_fast_bytes(K0, N));
   const float sp = *nb.sd, mp = *nb.mu;
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -901,7 +899,7 @@ template <int K0, int N>
 static int launch_dxnb(const Args& a, const NormBwd& nb, long blocks, hipStream_t st) {
   auto kern = dx_norm_bwd_kernel<K0, N>;
   RG_ENSURE_LDS(kern, DYN_LDS_MAX);
-  kern<<<blocks, FT, fbytes(K0, N), st>>>(a, nb);
+  kern<<<blocks, FT, f32_fast_bytes(K0, N), st>>>(a, nb);
   RG_LAUNCH_CHECK();
   return RG_OK;
 }

@@ -19,6 +19,7 @@
 //  * every layer's packed weights + bias live in LDS for the whole (persistent)
 //    workgroup: 8 waves, two per SIMD, share them; one 1-KiB ds_read_b128 feeds a
 //    32-cycle MFMA.
+#include "pack_layout.h"
 #include "rg_common.h"
 
 #define RG_HALF_F16 0

@@ -220,18 +220,15 @@ __device__ __forceinline__ void mfma_layer_rep(const bf16x8_t (&b)[REP * KS], f3
   }
 }
 
-// packed bytes of a fast-format Linear(K -> N): MT x KS fragments of 1 KiB + the
-// bias padded to N (rg_packed_linear_bytes, mlp_chain.hip); layer images are
-// 16-B aligned and back to back, so every LDS offset is a compile-time constant
-__host__ __device__ constexpr int fast_bytes(int K, int N) {
-  return (N / 32) * ((K + 15) / 16) * 1024 + N * 4;
-}
+// layer images (fast_bytes(K, N), pack_layout.h: MT x KS fragments of 1 KiB + the bias padded
+// to N) are 16-B aligned and back to back, so every LDS offset is a compile-time constant
 template <int N, int... Rest> struct FirstOf { static constexpr int value = N; };
 template <int K, int... Ns> struct Offsets;
 template <int K> struct Offsets<K> {
   static constexpr int get(int) { return 0; }
 };
 template <int K, int N, int... Rest> struct Offsets<K, N, Rest...> {
+  static_assert(N % 32 == 0, "a chain kernel's N is the layer's width padded to 32");
   static constexpr int get(int l) {
     return l == 0 ? 0 : ((fast_bytes(K, N) + 15) & ~15) + Offsets<N, Rest...>::get(l - 1);
   }
@@ -753,8 +750,7 @@ static int chain_fast_entry(const rg_layer* layers, int n_layers, long rows,
     a.L[l].mu = s.norm_mu;
     a.L[l].sd = s.norm_std;
     a.L[l].woff = off;
-    a.L[l].bytes = (int)rg_packed_linear_bytes(s.in_dim, s.out_dim,
-                                               l == 0 ? RG_PACK_FAST_IN : RG_PACK_FAST_CHAIN);
+    a.L[l].bytes = fast_bytes(s.in_dim, s.out_dim);
     a.L[l].out = s.out_dim;
     a.L[l].act = s.act;
     a.L[l].centered = (s.flags & RG_LAYER_CENTERED) ? 1 : 0;

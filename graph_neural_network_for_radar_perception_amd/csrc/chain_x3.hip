@@ -62,6 +62,7 @@ template <typename P, int K0, int... Ns>
 struct Shape {
   static constexpr int NL = sizeof...(Ns);
   static constexpr int N[NL] = {Ns...};
+  static_assert(((Ns % 32 == 0) && ...), "N: the layers' widths padded to whole 32-row M-tiles");
   static constexpr int K(int l) { return l == 0 ? K0 : N[l - 1]; }
   static constexpr int pl(int l) { return plane_bytes(K(l), N[l]); }
   static constexpr int bytes(int l) { return P::image_bytes(K(l), N[l]); }

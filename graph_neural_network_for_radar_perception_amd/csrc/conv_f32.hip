@@ -23,6 +23,7 @@
 // Two waves per SIMD (conv_f32_kernel2 below).  Workgroups are persistent; block ids come from one atomic counter per XCD over that
 // XCD's contiguous eighth of the nodes (workgroup w runs on XCD w % 8), so each frame's
 // x, P and Q rows are gathered from one L2.
+#include "pack_layout.h"
 #include "rg_common.h"
 
 #include <stdlib.h>
@@ -40,13 +41,11 @@ static constexpr int AS = 68;        // LDS row stride (floats) of the aggregate
 static constexpr float NORM_EPS = 1e-5f;
 static constexpr int NXCD = 8;
 
-__host__ __device__ constexpr int fbytes(int K, int N) {
-  return (N / 32) * ((K + 7) / 8) * 1024 + N * 4;
-}
+static_assert(C % 32 == 0 && HID % 32 == 0, "widths as packed: whole 32-row M-tiles");
 static constexpr int W_E_OFF = 0;                                       // W_e: 64 -> 128
-static constexpr int W_2_OFF = (fbytes(C, HID) + 15) & ~15;             // W_2: 128 -> 64
-static constexpr int W_U_OFF = W_2_OFF + ((fbytes(HID, C) + 15) & ~15);  // W_u: 128 -> 64
-static constexpr int W_BYTES = W_U_OFF + ((fbytes(2 * C, C) + 15) & ~15);
+static constexpr int W_2_OFF = (f32_fast_bytes(C, HID) + 15) & ~15;             // W_2: 128 -> 64
+static constexpr int W_U_OFF = W_2_OFF + ((f32_fast_bytes(HID, C) + 15) & ~15);  // W_u: 128 -> 64
+static constexpr int W_BYTES = W_U_OFF + ((f32_fast_bytes(2 * C, C) + 15) & ~15);
 static constexpr int WAVE_LDS = (16 * TS + NBLK * AS) * 4;
 static constexpr int LDS_BYTES = W_BYTES + NW * WAVE_LDS;
 static_assert(LDS_BYTES <= DYN_LDS_MAX, "conv_f32 LDS");
@@ -231,7 +230,7 @@ __global__ __launch_bounds__(FT2) void conv_f32_kernel2(Args a) {
     nrm[2 * threadIdx.x + 1] = *a.sd[threadIdx.x];
   }
   {
-    const int nb[2] = {fbytes(C, HID), fbytes(HID, C)};
+    const int nb[2] = {f32_fast_bytes(C, HID), f32_fast_bytes(HID, C)};
     const int off[2] = {W_E_OFF, W_2_OFF};
 #pragma unroll
     for (int l = 0; l < 2; ++l) {

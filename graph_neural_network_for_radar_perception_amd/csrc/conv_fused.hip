@@ -24,6 +24,7 @@
 //      norm + act + residual, store x_new[node].
 // Workgroups (8 waves, 2 per SIMD) are persistent and pull node blocks from an
 // atomic counter; all weights (81 KiB packed bf16 + biases) sit in LDS.
+#include "pack_layout.h"
 #include "rg_common.h"
 #include "scan.h"
 

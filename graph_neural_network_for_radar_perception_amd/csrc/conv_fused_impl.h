@@ -14,6 +14,7 @@ static constexpr int CW = CT / 64;
 static constexpr int NB = 8;         // destination nodes per work block
 static constexpr int C = 64;         // node / edge / message / output channels
 static constexpr int HID = 128;      // msg_mlp_hidden_dim
+static_assert(C % 32 == 0 && HID % 32 == 0, "widths as packed: whole 32-row M-tiles");
 // wave-private LDS: P (NB rows of HID f32, row stride PST: the 4-float pad puts the rows of
 // different nodes on different banks -- at HID they all mapped to the same four), message
 // tile (32 x C bf16)
@@ -633,14 +634,13 @@ static int conv_fused_entry(const rg_layer* msg_layers, const rg_layer* upd_laye
   CArgs a;
   memset(&a, 0, sizeof(a));
   const rg_layer* ls[3] = {&m0, &m1, &u};
-  const int fmts[3] = {RG_PACK_FAST_IN, RG_PACK_FAST_CHAIN, RG_PACK_FAST_UPD};
   int off = 0;
   for (int l = 0; l < 3; ++l) {
     a.L[l].src = ls[l]->w_packed;
     a.L[l].mu = ls[l]->norm_mu;
     a.L[l].sd = ls[l]->norm_std;
     a.L[l].woff = off;
-    a.L[l].bytes = (int)rg_packed_linear_bytes(ls[l]->in_dim, ls[l]->out_dim, fmts[l]);
+    a.L[l].bytes = fast_bytes(ls[l]->in_dim, ls[l]->out_dim);
     a.L[l].out = ls[l]->out_dim;
     a.L[l].act = ls[l]->act;
     a.L[l].centered = (ls[l]->flags & RG_LAYER_CENTERED) ? 1 : 0;

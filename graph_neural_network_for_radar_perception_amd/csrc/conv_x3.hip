@@ -49,6 +49,7 @@ using namespace ::rg::x3;
 static constexpr int C = 64;      // node / edge / message / output channels
 static constexpr int HID = 128;   // msg_mlp_hidden_dim
 static constexpr int PQW = 2 * HID;
+static_assert(C % 32 == 0 && HID % 32 == 0, "widths as packed: whole 32-row M-tiles");
 static constexpr int NBLK = 32;   // destination nodes per work block
 static constexpr int NXCD = 8;
 static constexpr int CTR_STRIDE = 32;  // block counters one 128-B line apart (per-line atomics)

@@ -22,6 +22,7 @@
 //
 // dtype RG_F32 : v_mfma_f32_16x16x4_f32  (exact f32 products, k-ordered fma chain)
 // dtype RG_BF16: v_mfma_f32_16x16x32_bf16 (bf16 operands, f32 accumulate and epilogue)
+#include "pack_layout.h"
 #include "rg_common.h"
 #include "x3_common.h"
 
@@ -44,28 +45,6 @@ template <> struct Cfg<uint16_t> {
   static constexpr int STRIDE = MAXW + 16;  // 544 B rows
 };
 template <> struct Cfg<_Float16> : Cfg<uint16_t> {};  // IEEE fp16 slab (RG_F16), bf16's layout
-
-__host__ __device__ inline int kpad(int k, int p) { return (k + p - 1) / p * p; }
-
-__host__ __device__ inline size_t frag_bytes(int in_dim, int out_dim, int dtype) {
-  if (dtype == RG_PACK_F32_FAST)
-    return (size_t)((out_dim + 31) / 32) * ((in_dim + 7) / 8) * 1024;
-  if (dtype == RG_PACK_FAST_IN || dtype == RG_PACK_FAST_CHAIN || dtype == RG_PACK_FAST_UPD)
-    return (size_t)((out_dim + 31) / 32) * ((in_dim + 15) / 16) * 64 * 8 * sizeof(uint16_t);
-  const size_t mt = (size_t)(out_dim + 15) / 16;
-  if (dtype == RG_F32) return mt * (kpad(in_dim, 16) / 16) * 64 * 4 * sizeof(float);
-  return mt * (kpad(in_dim, 32) / 32) * 64 * 8 * sizeof(uint16_t);
-}
-static size_t packed_bytes(int in_dim, int out_dim, int dtype) {
-  if (dtype & RG_PACK_H2)  // two fp16 planes, the scaled bias (accumulator order), the scale
-    return 2 * frag_bytes(in_dim, out_dim, dtype & ~RG_PACK_H2) +
-           (size_t)kpad(out_dim, 32) * sizeof(float) + 16;
-  if (dtype & RG_PACK_X3)  // three bf16 planes, then the bias (accumulator order)
-    return 3 * frag_bytes(in_dim, out_dim, dtype & ~RG_PACK_X3) + (size_t)kpad(out_dim, 32) * sizeof(float);
-  const int bpad = (dtype == RG_PACK_FAST_IN || dtype == RG_PACK_FAST_CHAIN ||
-                    dtype == RG_PACK_FAST_UPD || dtype == RG_PACK_F32_FAST) ? 32 : 16;
-  return frag_bytes(in_dim, out_dim, dtype) + (size_t)kpad(out_dim, bpad) * sizeof(float);
-}
 
 struct ChainLayer {
   const void* w;  // packed fragments, followed by the f32 bias padded to 16*mt
@@ -95,195 +74,6 @@ struct ChainArgs {
   const void* res;
   void* out;
 };
-
-// ------------------------------------------------------------------ packing
-// f32 : [m][s4][lane][4] = W[16m + (lane&15)][16*s4 + 4*(lane>>4) + t]
-// bf16: [m][s ][lane][8] = W[16m + (lane&15)][32*s  + 8*(lane>>4) + j]
-// weights, then the nb bias entries that follow them in the image (zeros without a bias):
-// one launch per packed f32 layer (the training step repacks every layer after each SGD step)
-__global__ void pack_f32_kernel(const float* __restrict__ W, int in, int out, int transpose,
-                                float* __restrict__ P, long total,
-                                const float* __restrict__ bias = nullptr, int nb = 0, int ld = 0) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) {
-    const long i = t - total;
-    if (i < nb) P[t] = (bias && i < out) ? bias[i] : 0.f;
-    return;
-  }
-  const int S4 = kpad(in, 16) / 16;
-  const int e = (int)(t & 3);
-  const int lane = (int)((t >> 2) & 63);
-  const long ms = t >> 8;
-  const int s4 = (int)(ms % S4);
-  const int m = (int)(ms / S4);
-  const int o = 16 * m + (lane & 15);
-  const int k = 16 * s4 + 4 * (lane >> 4) + e;
-  // transpose: W holds the [in][out] matrix whose transpose is the layer; ld: W's row stride
-  // (0: dense) -- a column block of a wider matrix
-  const int ldw = ld ? ld : (transpose ? out : in);
-  P[t] = (o < out && k < in) ? (transpose ? W[(size_t)k * ldw + o] : W[(size_t)o * ldw + k]) : 0.f;
-}
-
-// plane p > 0: the p-th term of the exact three-term bf16 split (RG_PACK_X3 | RG_BF16, the
-// generic chain's f32 arithmetic on bf16 products); transpose: W holds the [in][out] matrix
-// f16: IEEE fp16 fragments (RG_BF16 | RG_PACK_F16, the generic chain's fp16 operands)
-__global__ void pack_bf16_kernel(const float* __restrict__ W, int in, int out, int plane,
-                                 int transpose, uint16_t* __restrict__ P, long total, int f16 = 0) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int S = kpad(in, 32) / 32;
-  const int j = (int)(t & 7);
-  const int lane = (int)((t >> 3) & 63);
-  const long ms = t >> 9;
-  const int s = (int)(ms % S);
-  const int m = (int)(ms / S);
-  const int o = 16 * m + (lane & 15);
-  const int k = 32 * s + 8 * (lane >> 4) + j;
-  float v = 0.f;
-  if (o < out && k < in) v = transpose ? W[(size_t)k * out + o] : W[(size_t)o * in + k];
-  for (int q = 0; q < plane; ++q) v -= bf16_to_f32(f32_to_bf16(v));  // exact residues
-  P[t] = f16 ? f32_to_f16(v) : f32_to_bf16(v);
-}
-
-// 32x32x16 fragments: [m][s][lane][8] = W[32m + (lane&31)][k(s, lane>>5, j)] with
-// FAST_IN   k = 16s + 8h + j                                  (operand loaded from memory)
-// FAST_CHAIN k = 32(s>>1) + 16(s&1) + 8(j>>2) + 4h + (j&3)    (operand = previous layer's
-//            accumulator registers 8(s&1)..8(s&1)+7 of M-tile s>>1, no lane movement)
-// FAST_UPD  k-steps s < in/32 as FAST_IN (x[node] from memory), the rest as FAST_CHAIN
-//           offset by in/2 (aggregate from accumulators): the fused conv layer's update
-// plane p > 0 (RG_PACK_X3): the p-th bf16 term of the exact three-term split of each
-// weight, w = bf16(w) + bf16(w - w0) + bf16(w - w0 - w1) (conv_x3.hip)
-// f16 (RG_PACK_F16): IEEE fp16 fragments instead of bf16
-// element t of a fast-format plane: the (centred) weight it holds, 0 in the padding
-__device__ inline float fast_elem(const float* __restrict__ W, int in, int out, int mem_steps,
-                                  int center, long t) {
-  const int S = (in + 15) / 16;
-  const int j = (int)(t & 7);
-  const int lane = (int)((t >> 3) & 63);
-  const long ms = t >> 9;
-  const int s = (int)(ms % S);
-  const int m = (int)(ms / S);
-  const int h = lane >> 5;
-  const int o = 32 * m + (lane & 31);
-  const int sc = s - mem_steps;
-  const int k = s < mem_steps
-                    ? 16 * s + 8 * h + j
-                    : 16 * mem_steps + 32 * (sc >> 1) + 16 * (sc & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-  float v = 0.f;
-  if (o < out && k < in) {
-    v = W[(size_t)o * in + k];
-    if (center) {  // RG_PACK_CENTERED: subtract the mean over the outputs of column k
-      float cs = 0.f;
-      for (int oo = 0; oo < out; ++oo) cs += W[(size_t)oo * in + k];
-      v -= cs / (float)out;
-    }
-  }
-  return v;
-}
-__global__ void pack_fast_kernel(const float* __restrict__ W, int in, int out, int mem_steps,
-                                 int center, int plane, int f16, uint16_t* __restrict__ P,
-                                 long total) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  float v = fast_elem(W, in, out, mem_steps, center, t);
-  for (int q = 0; q < plane; ++q) v -= bf16_to_f32(f32_to_bf16(v));  // exact residues
-  P[t] = f16 ? f32_to_f16(v) : f32_to_bf16(v);
-}
-
-// RG_PACK_H2: the layer's power-of-two scale from max |w| (centred as the planes are), one
-// workgroup; tr = {2^-s, 2^s, (int) s, 0} with max |w| 2^s in [2^12, 2^13), |s| <= 64
-static constexpr int H2_SMAX = 64;
-__global__ void h2_scale_kernel(const float* __restrict__ W, int in, int out, int center,
-                                float* __restrict__ tr) {
-  __shared__ float red[256];
-  float mx = 0.f;
-  for (int k = threadIdx.x; k < in; k += 256) {
-    float mean = 0.f;
-    if (center) {  // the same sum, in the same order, as fast_elem's
-      float cs = 0.f;
-      for (int oo = 0; oo < out; ++oo) cs += W[(size_t)oo * in + k];
-      mean = cs / (float)out;
-    }
-    for (int o = 0; o < out; ++o) {
-      const float v = center ? W[(size_t)o * in + k] - mean : W[(size_t)o * in + k];
-      mx = fmaxf(mx, fabsf(v));
-    }
-  }
-  red[threadIdx.x] = mx;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    int s = 0;
-    if (red[0] > 0.f && red[0] < INFINITY) {
-      int e;
-      frexpf(red[0], &e);  // max = m 2^e, m in [0.5, 1): max 2^(13 - e) in [2^12, 2^13)
-      s = min(max(13 - e, -H2_SMAX), H2_SMAX);
-    }
-    tr[0] = ldexpf(1.f, -s);
-    tr[1] = ldexpf(1.f, s);
-    ((int*)tr)[2] = s;
-    tr[3] = 0.f;
-  }
-}
-// plane 0: fp16(w 2^s), plane 1: fp16(w 2^s - plane 0) (the residue exact in f32)
-__global__ void pack_fast_h2_kernel(const float* __restrict__ W, int in, int out, int mem_steps,
-                                    int center, int plane, const float* __restrict__ tr,
-                                    uint16_t* __restrict__ P, long total) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  float v = fast_elem(W, in, out, mem_steps, center, t) * tr[1];
-  if (plane) v -= f16_to_f32(f32_to_f16(v));
-  P[t] = f32_to_f16(v);
-}
-
-// RG_PACK_F32_FAST: [m][s4][lane][4] = W[32m + (lane&31)][8 s4 + 4 (lane>>5) + u]; the k
-// order is what both a row loaded from memory (one float4 per lane half and s4) and the
-// previous layer's 32x32 accumulators (register 4g + t of M-tile m' = k-step
-// 16 m' + 4g + t) supply, so one format serves every layer of an f32 chain
-__global__ void pack_f32_fast_kernel(const float* __restrict__ W, int in, int out, int transpose,
-                                     float* __restrict__ P, long total, int ld = 0) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int S4 = (in + 7) / 8;
-  const int u = (int)(t & 3);
-  const int lane = (int)((t >> 2) & 63);
-  const long ms = t >> 8;
-  const int s4 = (int)(ms % S4);
-  const int m = (int)(ms / S4);
-  const int o = 32 * m + (lane & 31);
-  const int k = 8 * s4 + 4 * (lane >> 5) + u;
-  // transpose: W is the [in][out] weight of the forward layer, packed as its transpose;
-  // ld: W's row stride (0: dense)
-  const int ldw = ld ? ld : (transpose ? out : in);
-  P[t] = (o < out && k < in) ? (transpose ? W[(size_t)k * ldw + o] : W[(size_t)o * ldw + k]) : 0.f;
-}
-
-__global__ void pack_bias_kernel(const float* __restrict__ b, int out, int n, float* __restrict__ P) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) P[t] = (b && t < out) ? b[t] : 0.f;
-}
-
-// fast formats: the bias in 32x32 accumulator order, [m][h][16] with entry
-// 4g + j = bias[32m + 8g + 4h + j], so lane half h of M-tile m initialises its 16
-// accumulators with four contiguous 16-B LDS reads (no register moves)
-// tr (RG_PACK_H2): the layer's scale trailer; the bias is stored times 2^s (exact)
-__global__ void pack_bias_frag_kernel(const float* __restrict__ b, int out, int n, int center,
-                                      float* __restrict__ P, const float* __restrict__ tr = nullptr) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int m = t >> 5, h = (t >> 4) & 1, g = (t >> 2) & 3, j = t & 3;
-  const int f = 32 * m + 8 * g + 4 * h + j;
-  float v = (b && f < out) ? b[f] : 0.f;
-  if (center && b && f < out) {
-    float cs = 0.f;
-    for (int o = 0; o < out; ++o) cs += b[o];
-    v -= cs / (float)out;
-  }
-  P[t] = tr ? v * tr[1] : v;
-}
 
 // ------------------------------------------------------------------ element access
 __device__ __forceinline__ float ld_elem(const void* p, int dt, size_t i) {
@@ -705,216 +495,6 @@ static int launch_chain(const ChainArgs& a, long rows, hipStream_t st) {
 
 using namespace rg;
 
-extern "C" size_t rg_packed_linear_bytes(int in_dim, int out_dim, int dtype) {
-  return packed_bytes(in_dim, out_dim, dtype & ~(RG_PACK_CENTERED | RG_PACK_TRANSPOSE | RG_PACK_F16));
-}
-
-// RG_PACK_H2: two scaled fp16 planes of one RG_PACK_FAST_IN / _CHAIN format, the scaled bias,
-// the scale
-static int pack_h2(const float* weight, const float* bias, int in_dim, int out_dim, int fmt,
-                   int center, void* packed, hipStream_t st) {
-  RG_REQUIRE(fmt == RG_PACK_FAST_IN || fmt == RG_PACK_FAST_CHAIN, RG_ERR_ARG,
-             "rg_pack_linear: RG_PACK_H2 applies to RG_PACK_FAST_IN and RG_PACK_FAST_CHAIN");
-  const int ks = (in_dim + 15) / 16;
-  const int mem_steps = fmt == RG_PACK_FAST_IN ? ks : 0;
-  const size_t fb = frag_bytes(in_dim, out_dim, fmt);
-  const long total = (long)fb / sizeof(uint16_t);
-  const int nb = kpad(out_dim, 32);
-  float* pb = (float*)((char*)packed + 2 * fb);
-  float* tr = pb + nb;
-  h2_scale_kernel<<<1, 256, 0, st>>>(weight, in_dim, out_dim, center, tr);
-  for (int p = 0; p < 2; ++p)
-    pack_fast_h2_kernel<<<ceil_div(total, 256), 256, 0, st>>>(
-        weight, in_dim, out_dim, mem_steps, center, p, tr, (uint16_t*)((char*)packed + p * fb), total);
-  pack_bias_frag_kernel<<<ceil_div(nb, 256), 256, 0, st>>>(bias, out_dim, nb, center, pb, tr);
-  RG_LAUNCH_CHECK();
-  return RG_OK;
-}
-
-// RG_PACK_X3: three planes of one RG_PACK_FAST_* format, or of RG_BF16 (the generic chain's
-// 16x16x32 fragments; transpose allowed), then the f32 bias
-static int pack_x3(const float* weight, const float* bias, int in_dim, int out_dim, int fmt,
-                   int center, int transpose, void* packed, hipStream_t st) {
-  if (fmt == RG_BF16) {
-    RG_REQUIRE(!center, RG_ERR_ARG, "rg_pack_linear: RG_PACK_CENTERED applies to the fast formats");
-    const size_t fb = frag_bytes(in_dim, out_dim, RG_BF16);
-    const long total = (long)fb / sizeof(uint16_t);
-    for (int p = 0; p < 3; ++p)
-      pack_bf16_kernel<<<ceil_div(total, 256), 256, 0, st>>>(
-          weight, in_dim, out_dim, p, transpose, (uint16_t*)((char*)packed + p * fb), total);
-    const int nb = kpad(out_dim, 32);
-    pack_bias_kernel<<<ceil_div(nb, 256), 256, 0, st>>>(bias, out_dim, nb,
-                                                        (float*)((char*)packed + 3 * fb));
-    RG_LAUNCH_CHECK();
-    return RG_OK;
-  }
-  RG_REQUIRE(!transpose, RG_ERR_ARG,
-             "rg_pack_linear: RG_PACK_X3 with RG_PACK_TRANSPOSE applies to RG_BF16");
-  RG_REQUIRE(fmt == RG_PACK_FAST_IN || fmt == RG_PACK_FAST_CHAIN || fmt == RG_PACK_FAST_UPD,
-             RG_ERR_ARG, "rg_pack_linear: RG_PACK_X3 applies to RG_BF16 and the RG_PACK_FAST_* formats");
-  const int ks = (in_dim + 15) / 16;
-  RG_REQUIRE(fmt != RG_PACK_FAST_UPD || in_dim % 64 == 0, RG_ERR_ARG,
-             "RG_PACK_FAST_UPD needs in_dim = 2*C with C a multiple of 32");
-  const int mem_steps = fmt == RG_PACK_FAST_IN ? ks : (fmt == RG_PACK_FAST_CHAIN ? 0 : ks / 2);
-  const size_t fb = frag_bytes(in_dim, out_dim, fmt);
-  const long total = (long)fb / sizeof(uint16_t);
-  for (int p = 0; p < 3; ++p)
-    pack_fast_kernel<<<ceil_div(total, 256), 256, 0, st>>>(weight, in_dim, out_dim, mem_steps,
-                                                           center, p, 0,
-                                                           (uint16_t*)((char*)packed + p * fb), total);
-  const int nb = kpad(out_dim, 32);
-  pack_bias_frag_kernel<<<ceil_div(nb, 256), 256, 0, st>>>(bias, out_dim, nb, center,
-                                                           (float*)((char*)packed + 3 * fb));
-  RG_LAUNCH_CHECK();
-  return RG_OK;
-}
-
-extern "C" int rg_pack_linear(const float* weight, const float* bias, int in_dim, int out_dim,
-                              int dtype, void* packed, void* stream) {
-  RG_REQUIRE(in_dim > 0 && out_dim > 0 && in_dim <= MAXW && out_dim <= MAXW, RG_ERR_UNSUPPORTED,
-             "rg_pack_linear: dims %dx%d outside 1..%d", out_dim, in_dim, MAXW);
-  hipStream_t st = (hipStream_t)stream;
-  const int f16 = (dtype & RG_PACK_F16) ? 1 : 0;
-  dtype &= ~RG_PACK_F16;
-  RG_REQUIRE(!f16 || dtype == RG_BF16 || ((dtype & ~RG_PACK_CENTERED) >= RG_PACK_FAST_IN &&
-                                          (dtype & ~RG_PACK_CENTERED) <= RG_PACK_FAST_UPD),
-             RG_ERR_ARG, "rg_pack_linear: RG_PACK_F16 applies to RG_BF16 and the RG_PACK_FAST_* formats");
-  if (dtype & RG_PACK_H2) {
-    RG_REQUIRE(!f16 && !(dtype & (RG_PACK_X3 | RG_PACK_TRANSPOSE)), RG_ERR_ARG,
-               "rg_pack_linear: RG_PACK_H2 excludes RG_PACK_X3, RG_PACK_F16 and RG_PACK_TRANSPOSE");
-    return pack_h2(weight, bias, in_dim, out_dim, dtype & ~(RG_PACK_H2 | RG_PACK_CENTERED),
-                   (dtype & RG_PACK_CENTERED) ? 1 : 0, packed, st);
-  }
-  if (dtype & RG_PACK_X3) {
-    return pack_x3(weight, bias, in_dim, out_dim,
-                   dtype & ~(RG_PACK_X3 | RG_PACK_CENTERED | RG_PACK_TRANSPOSE),
-                   (dtype & RG_PACK_CENTERED) ? 1 : 0, (dtype & RG_PACK_TRANSPOSE) ? 1 : 0, packed,
-                   st);
-  }
-  const int center = (dtype & RG_PACK_CENTERED) ? 1 : 0;
-  const int transpose = (dtype & RG_PACK_TRANSPOSE) ? 1 : 0;
-  dtype &= ~(RG_PACK_CENTERED | RG_PACK_TRANSPOSE);
-  RG_REQUIRE(!transpose || dtype == RG_F32 || dtype == RG_PACK_F32_FAST, RG_ERR_ARG,
-             "rg_pack_linear: RG_PACK_TRANSPOSE applies to RG_F32 and RG_PACK_F32_FAST");
-  RG_REQUIRE(!center || (dtype >= RG_PACK_FAST_IN && dtype <= RG_PACK_FAST_UPD), RG_ERR_ARG,
-             "rg_pack_linear: RG_PACK_CENTERED applies to the bf16 RG_PACK_FAST_* formats");
-  if (dtype == RG_F32) {
-    // weights and bias in one launch (the bias follows the weights: pb below)
-    const long total = (long)frag_bytes(in_dim, out_dim, dtype) / sizeof(float);
-    const int nb = kpad(out_dim, 16);
-    pack_f32_kernel<<<ceil_div(total + nb, 256), 256, 0, st>>>(weight, in_dim, out_dim, transpose,
-                                                               (float*)packed, total, bias, nb);
-    RG_LAUNCH_CHECK();
-    return RG_OK;
-  }
-  if (dtype == RG_BF16) {
-    long total = (long)frag_bytes(in_dim, out_dim, dtype) / sizeof(uint16_t);
-    pack_bf16_kernel<<<ceil_div(total, 256), 256, 0, st>>>(weight, in_dim, out_dim, 0, 0,
-                                                           (uint16_t*)packed, total, f16);
-  } else if (dtype == RG_PACK_FAST_IN || dtype == RG_PACK_FAST_CHAIN || dtype == RG_PACK_FAST_UPD) {
-    long total = (long)frag_bytes(in_dim, out_dim, dtype) / sizeof(uint16_t);
-    const int ks = (in_dim + 15) / 16;
-    RG_REQUIRE(dtype != RG_PACK_FAST_UPD || in_dim % 64 == 0, RG_ERR_ARG,
-               "RG_PACK_FAST_UPD needs in_dim = 2*C with C a multiple of 32");
-    const int mem_steps = dtype == RG_PACK_FAST_IN ? ks : (dtype == RG_PACK_FAST_CHAIN ? 0 : ks / 2);
-    pack_fast_kernel<<<ceil_div(total, 256), 256, 0, st>>>(weight, in_dim, out_dim, mem_steps,
-                                                           center, 0, f16, (uint16_t*)packed,
-                                                           total);
-  } else if (dtype == RG_PACK_F32_FAST) {
-    long total = (long)frag_bytes(in_dim, out_dim, dtype) / sizeof(float);
-    pack_f32_fast_kernel<<<ceil_div(total, 256), 256, 0, st>>>(weight, in_dim, out_dim, transpose,
-                                                               (float*)packed, total);
-  } else {
-    RG_REQUIRE(false, RG_ERR_ARG, "rg_pack_linear: bad dtype %d", dtype);
-  }
-  const int nb = kpad(out_dim, (dtype >= RG_PACK_FAST_IN) ? 32 : 16);
-  float* pb = (float*)((char*)packed + frag_bytes(in_dim, out_dim, dtype));
-  if (dtype >= RG_PACK_FAST_IN)
-    pack_bias_frag_kernel<<<ceil_div(nb, 256), 256, 0, st>>>(bias, out_dim, nb, center, pb);
-  else
-    pack_bias_kernel<<<ceil_div(nb, 256), 256, 0, st>>>(bias, out_dim, nb, pb);
-  RG_LAUNCH_CHECK();
-  return RG_OK;
-}
-
-extern "C" int rg_pack_linear_ld(const float* weight, const float* bias, int in_dim, int out_dim,
-                                 int dtype, int ld, void* packed, void* stream) {
-  const int transpose = (dtype & RG_PACK_TRANSPOSE) ? 1 : 0;
-  const int fmt = dtype & ~RG_PACK_TRANSPOSE;
-  RG_REQUIRE(fmt == RG_F32 || fmt == RG_PACK_F32_FAST, RG_ERR_ARG,
-             "rg_pack_linear_ld: RG_F32 or RG_PACK_F32_FAST (| RG_PACK_TRANSPOSE)");
-  RG_REQUIRE(in_dim > 0 && out_dim > 0 && in_dim <= MAXW && out_dim <= MAXW, RG_ERR_UNSUPPORTED,
-             "rg_pack_linear_ld: dims %dx%d outside 1..%d", out_dim, in_dim, MAXW);
-  RG_REQUIRE(ld == 0 || ld >= (transpose ? out_dim : in_dim), RG_ERR_ARG,
-             "rg_pack_linear_ld: ld %d shorter than a row", ld);
-  hipStream_t st = (hipStream_t)stream;
-  const long total = (long)frag_bytes(in_dim, out_dim, fmt) / sizeof(float);
-  if (fmt == RG_F32) {
-    const int nb = kpad(out_dim, 16);
-    pack_f32_kernel<<<ceil_div(total + nb, 256), 256, 0, st>>>(weight, in_dim, out_dim, transpose,
-                                                               (float*)packed, total, bias, nb, ld);
-  } else {
-    pack_f32_fast_kernel<<<ceil_div(total, 256), 256, 0, st>>>(weight, in_dim, out_dim, transpose,
-                                                               (float*)packed, total, ld);
-    const int nb = kpad(out_dim, 32);
-    pack_bias_frag_kernel<<<ceil_div(nb, 256), 256, 0, st>>>(
-        bias, out_dim, nb, 0, (float*)((char*)packed + frag_bytes(in_dim, out_dim, fmt)));
-  }
-  RG_LAUNCH_CHECK();
-  return RG_OK;
-}
-
-// rg_pack_linear_jobs: blockIdx.y = job, a grid-stride loop over its weights then its bias
-// (RG_F32: plain, padded to 16; RG_PACK_F32_FAST: accumulator order, padded to 32) -- the same
-// element formulas as pack_f32_kernel / pack_f32_fast_kernel / pack_bias_frag_kernel
-__global__ void pack_jobs_kernel(const rg_pack_job* __restrict__ jobs) {
-  const rg_pack_job j = jobs[blockIdx.y];
-  const bool fast = j.fmt == RG_PACK_F32_FAST;
-  const long total = (long)frag_bytes(j.in_dim, j.out_dim, j.fmt) / sizeof(float);
-  const int nb = kpad(j.out_dim, fast ? 32 : 16);
-  float* P = (float*)j.packed;
-  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total + nb;
-       t += (long)gridDim.x * blockDim.x) {
-    if (t >= total) {
-      const int i = (int)(t - total);
-      int f = i;
-      if (fast) {
-        const int m = i >> 5, h = (i >> 4) & 1, g = (i >> 2) & 3, q = i & 3;
-        f = 32 * m + 8 * g + 4 * h + q;
-      }
-      P[t] = (j.bias && f < j.out_dim) ? j.bias[f] : 0.f;
-      continue;
-    }
-    const int e = (int)(t & 3);
-    const int lane = (int)((t >> 2) & 63);
-    const long ms = t >> 8;
-    int o, k;
-    if (fast) {
-      const int S4 = (j.in_dim + 7) / 8;
-      o = 32 * (int)(ms / S4) + (lane & 31);
-      k = 8 * (int)(ms % S4) + 4 * (lane >> 5) + e;
-    } else {
-      const int S4 = kpad(j.in_dim, 16) / 16;
-      o = 16 * (int)(ms / S4) + (lane & 15);
-      k = 16 * (int)(ms % S4) + 4 * (lane >> 4) + e;
-    }
-    const int ldw = j.ld ? j.ld : (j.transpose ? j.out_dim : j.in_dim);
-    P[t] = (o < j.out_dim && k < j.in_dim)
-               ? (j.transpose ? j.weight[(size_t)k * ldw + o] : j.weight[(size_t)o * ldw + k])
-               : 0.f;
-  }
-}
-
-extern "C" int rg_pack_linear_jobs(const rg_pack_job* jobs, int n_jobs, void* stream) {
-  RG_REQUIRE(n_jobs >= 0 && n_jobs <= 65535 && (jobs || n_jobs == 0), RG_ERR_ARG,
-             "rg_pack_linear_jobs: %d jobs", n_jobs);
-  if (n_jobs == 0) return RG_OK;
-  // 64 blocks of 256 per job: the largest f32 image (256 x 256 + bias) in four passes
-  pack_jobs_kernel<<<dim3(64, n_jobs), 256, 0, (hipStream_t)stream>>>(jobs);
-  RG_LAUNCH_CHECK();
-  return RG_OK;
-}
-
 extern "C" int rg_mlp_chain(int dtype, const rg_layer* layers, int n_layers, long rows,
                             const int* rows_dev, int in_mode, int in_dtype, const void* in0,
                             int ld0, int w0, const void* in1, int ld1, int w1, const void* in2,
@@ -966,7 +546,7 @@ extern "C" int rg_mlp_chain(int dtype, const rg_layer* layers, int n_layers, lon
     a.L[l].out = s.out_dim;
     a.L[l].act = s.act;
     a.L[l].woff = (int)woff;
-    woff += packed_bytes(s.in_dim, s.out_dim, wfmt);
+    woff += image_bytes(s.in_dim, s.out_dim, wfmt);
   }
   a.wbytes = (int)woff;
   a.nl = n_layers;

@@ -222,7 +222,7 @@ __device__ __forceinline__ float add_xor32(float x) {
 }
 
 // the 16 bias values of M-tile m, lane half h, from a fast-format bias stored in
-// accumulator order (rg_pack_linear, pack_bias_frag_kernel): four 16-B reads
+// accumulator order (rg_pack_linear; pack_layout.h, bias_acc): four 16-B reads
 __device__ __forceinline__ f32x16 ld_bias_frag(const float* bias, int m, int h) {
   const f32x4* p = (const f32x4*)(bias + (2 * m + h) * 16);
   const f32x4 a = p[0], b = p[1], c = p[2], d = p[3];

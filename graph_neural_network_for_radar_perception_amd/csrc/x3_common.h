@@ -39,6 +39,7 @@
 // {32m + 8(q >> 2) + 4h + (q & 3)} in register q.
 #pragma once
 
+#include "pack_layout.h"
 #include "rg_common.h"
 
 namespace rg {
@@ -49,13 +50,7 @@ typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-__host__ __device__ constexpr int plane_bytes(int K, int N) { return (N / 32) * ((K + 15) / 16) * 1024; }
-__host__ __device__ constexpr int x3_bytes(int K, int N) { return 3 * plane_bytes(K, N) + N * 4; }
-// h2 image: two planes, the bias times 2^s, then {2^-s, 2^s, (int) s, 0}
-static constexpr int H2_TRAILER = 16;
-__host__ __device__ constexpr int h2_bytes(int K, int N) {
-  return 2 * plane_bytes(K, N) + N * 4 + H2_TRAILER;
-}
+// image sizes (plane_bytes, x3_bytes, h2_bytes and their tails): pack_layout.h
 __host__ __device__ constexpr int al16(int b) { return (b + 15) & ~15; }
 
 __device__ __forceinline__ bf16x8_t ld_bf8(const char* p) {
@@ -184,7 +179,7 @@ struct B3 {
   static constexpr int wp(int i) { return i == 0 ? 2 : (i == 1 || i == 3) ? 1 : 0; }
   static constexpr int bp(int i) { return i == 2 ? 2 : (i == 1 || i == 4) ? 1 : 0; }
   static constexpr int image_bytes(int K, int N) { return x3_bytes(K, N); }
-  static constexpr int tail_bytes(int N) { return N * 4; }  // what follows the planes
+  static constexpr int tail_bytes(int N) { return x3_tail_bytes(N); }  // what follows the planes
   static __device__ __forceinline__ vec term(const X3& b, int i) {
     return i == 0 ? b.p0 : i == 1 ? b.p1 : b.p2;
   }
@@ -200,7 +195,7 @@ struct H2P {
   static constexpr int wp(int i) { return i == 0 ? 1 : 0; }
   static constexpr int bp(int i) { return i == 1 ? 1 : 0; }
   static constexpr int image_bytes(int K, int N) { return h2_bytes(K, N); }
-  static constexpr int tail_bytes(int N) { return N * 4 + H2_TRAILER; }
+  static constexpr int tail_bytes(int N) { return h2_tail_bytes(N); }
   static __device__ __forceinline__ vec term(const H2& b, int i) { return i == 0 ? b.p0 : b.p1; }
   static __device__ __forceinline__ vec cast(u32x4 u) { return __builtin_bit_cast(vec, u); }
   static __device__ __forceinline__ f32x16 mfma(vec a, vec b, f32x16 c) {

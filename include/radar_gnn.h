@@ -251,7 +251,10 @@ size_t rg_packed_linear_bytes(int in_dim, int out_dim, int dtype);
 
 /* Pack a torch nn.Linear (weight float32 [out_dim][in_dim] row-major, bias
  * float32[out_dim] or NULL; device) into the MFMA fragment order the chain
- * kernels read, zero padded, followed by the bias padded to a multiple of 16. */
+ * kernels read, zero padded, followed by the float32 bias: in plain order padded to a
+ * multiple of 16 for RG_F32 and RG_BF16 (32 with RG_PACK_X3), in 32x32 accumulator order
+ * padded to a multiple of 32 for RG_PACK_F32_FAST and the RG_PACK_FAST_* formats.  An
+ * RG_PACK_H2 image ends with its 16-byte scale trailer. */
 int rg_pack_linear(const float* weight, const float* bias, int in_dim, int out_dim, int dtype,
                    void* packed, void* stream);
 
