@@ -1,5 +1,12 @@
-// Float32 residual_graph_conv_block (gnn_blocks.py:96-113) on the bf16 matrix cores:
-// every f32 operand is split EXACTLY into three bf16 terms, v = v0 + v1 + v2 (round to
+// Float32 residual_graph_conv_block (gnn_blocks.py:96-113) on the 16-bit matrix cores under
+// one of the two term schemes of x3_common.h -- every kernel below is a template of it.
+// h2 (H2P, the shipped packing): two IEEE f16 terms, three products; the five images of a
+// layer each carry their own power-of-two scale 2^s, taken out where the chains take it out
+// (the norms' row scale), and P | Q rows are WRITTEN times 2^(s_e) of the W_e image that will
+// accumulate onto them (proj_x3_kernel / the previous layer's node launch multiply their
+// accumulators, which hold the rows times 2^(s_pq), by 2^(s_e - s_pq): exact), so the edge
+// launch's accumulators start as (P + Q) 2^(s_e) at no cost in its tile loop.
+// b3 (B3): every f32 operand is split EXACTLY into three bf16 terms, v = v0 + v1 + v2 (round to
 // nearest even at each step: v0 = bf16(v), v1 = bf16(v - v0), v2 = bf16(v - v0 - v1); the
 // residues are exact in f32 and the third term holds the last 8 significant bits), and a
 // product a.b is formed from the six terms of weight <= 2,
@@ -63,24 +70,48 @@ static constexpr bool STEAL = true;
 static constexpr int TR = 16;     // message rows per LDS transposition pass
 static constexpr int TS = 68;     // LDS row stride (floats) of the message tile
 
-static constexpr int WE_OFF = 0;                                   // W_e 64 -> 128 (FAST_IN)
-static constexpr int W2_OFF = al16(x3_bytes(C, HID));              // W_2 128 -> 64 (FAST_CHAIN)
-static constexpr int W_LDS = W2_OFF + al16(x3_bytes(HID, C));
 static constexpr int T_BYTES = TR * TS * 4;
-static constexpr int LDS_BYTES = W_LDS + NW * T_BYTES;
-static_assert(LDS_BYTES <= DYN_LDS_MAX, "conv_x3 LDS");
+// LDS of conv_x3_kernel under scheme P
+template <typename P>
+struct Blk {
+  static constexpr int WE_OFF = 0;                                   // W_e 64 -> 128 (FAST_IN)
+  static constexpr int W2_OFF = al16(P::image_bytes(C, HID));        // W_2 128 -> 64 (FAST_CHAIN)
+  static constexpr int W_LDS = W2_OFF + al16(P::image_bytes(HID, C));
+  static constexpr int LDS_BYTES = W_LDS + NW * T_BYTES;
+  static_assert(LDS_BYTES <= DYN_LDS_MAX, "conv_x3 LDS");
+};
+// the scale trailer {2^-s, 2^s, (int) s, 0} of a K -> N image of a scaled scheme (after the
+// planes and the bias, pack_layout.h)
+template <typename P>
+__device__ __forceinline__ const float* trailer(const char* img, int K, int N) {
+  return (const float*)(img + P::NP * plane_bytes(K, N) + N * 4);
+}
+// 2^-s of an image (1 under an unscaled scheme)
+template <typename P>
+__device__ __forceinline__ float descale(const char* img, int K, int N) {
+  if constexpr (P::SCALED) return trailer<P>(img, K, N)[0];
+  return 1.f;
+}
+// what a writer of P | Q rows multiplies its accumulators by: they hold the rows times
+// 2^(s_pq) and the consumer's edge launch wants them times 2^(s_e) of its W_e image
+template <typename P>
+__device__ __forceinline__ float pq_rescale(const char* wpq, const char* we) {
+  if constexpr (P::SCALED) return trailer<P>(wpq, C, PQW)[0] * trailer<P>(we, C, HID)[1];
+  return 1.f;
+}
 
 // P' | Q' of 32 rows held in accumulator layout (xo[2]: features 32m + 8g + 4h + t at
 // register 4g + t of tile m) -> pq rows [256] f32; W'_pq packed FAST_CHAIN x3 (K = 64): the
 // row's B operand is split once, then four passes of two M-tiles keep the live registers
 // bounded
-template <typename WSrc>
+// (k: pq_rescale, applied at the store under a scaled scheme)
+template <typename P, typename WSrc>
 __device__ __forceinline__ void project_rows(const f32x16 (&xo)[2], const WSrc& W, const float* bias,
-                                             float* pq_row, bool valid, int lane) {
+                                             float k, float* pq_row, bool valid, int lane) {
   const int h = lane >> 5;
-  X3 b[4];
+  typename P::terms b[4];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) b[s] = split_acc(xo[s >> 1], s & 1);
+  for (int s = 0; s < 4; ++s) b[s] = split_acc_of<P>(xo[s >> 1], s & 1);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     f32x16 acc[2];
@@ -92,7 +123,8 @@ __device__ __forceinline__ void project_rows(const f32x16 (&xo)[2], const WSrc& 
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const f32x4 v = {acc[m][4 * g], acc[m][4 * g + 1], acc[m][4 * g + 2], acc[m][4 * g + 3]};
+          f32x4 v = {acc[m][4 * g], acc[m][4 * g + 1], acc[m][4 * g + 2], acc[m][4 * g + 3]};
+          if constexpr (P::SCALED) v *= k;
           *(f32x4*)(pq_row + 64 * q + 32 * m + 8 * g + 4 * h) = v;
         }
     }
@@ -112,6 +144,7 @@ struct Args {
   int* counters;         // NXCD block counters + done counter, CTR_STRIDE apart; zero at launch
   const char* w[3];      // W_e (FAST_IN), W_2 (FAST_CHAIN), W_u (FAST_IN over cat(x, agg)), x3
   const char* wpq;       // the next layer's projection (FAST_CHAIN x3) or null
+  const char* we_next;   // the next layer's W_e image (scaled schemes: its scale, pq_rescale)
   const float* mu[3];
   const float* sd[3];
   int ldx, lde, ldo;
@@ -151,10 +184,11 @@ __device__ __forceinline__ void load_node_rows(const Args& a, int n0, int n1, in
 // ---- update MLP on cat(x[node], agg[node]) + residual (gnn_blocks.py:103-109) for the 32
 //      nodes n0 .. n1 - 1 (lane r = node) from their loaded rows, then -- when a.pq_out is
 //      set -- the next layer's projections from the same registers
-template <bool CENT, typename WU, typename WP>
+template <typename P, bool CENT, typename WU, typename WP>
 __device__ __forceinline__ void node_compute(const Args& a, const NodeRows& w, int n0, int n1,
                                              const WU& wU, const float* biasU, const WP& wPQ,
-                                             const float* biasPQ, float muU, float sdU, int lane) {
+                                             const float* biasPQ, float muU, float sdU, float dsU,
+                                             float kPQ, int lane) {
   const int r = lane & 31, h = lane >> 5;
   const int node = n0 + r;
   const bool nvalid = node < n1;
@@ -177,9 +211,9 @@ __device__ __forceinline__ void node_compute(const Args& a, const NodeRows& w, i
 #pragma unroll
   for (int m = 0; m < 2; ++m) accu[m] = ld_bias_frag(biasU, m, h);
   layer_x3<8, 2, 2, true>(accu, wU, 0, [&](int s) {
-    return s < 4 ? split8(w.xb[s][0], w.xb[s][1]) : split8(ab[s - 4][0], ab[s - 4][1]);
+    return s < 4 ? P::split(w.xb[s][0], w.xb[s][1]) : P::split(ab[s - 4][0], ab[s - 4][1]);
   });
-  norm_leaky<2, CENT>(accu, muU, sdU);
+  norm_leaky<2, CENT, P::SCALED>(accu, muU, sdU, dsU);  // true units from here on
   {
     // the residual x[node] in accumulator order (features 32 m + 8 g + 4 h + t) from the
     // k-order rows already in registers (features 16 s + 8 h + 4 u + t): the value lives in
@@ -206,27 +240,32 @@ __device__ __forceinline__ void node_compute(const Args& a, const NodeRows& w, i
         *(f32x4*)(po + 32 * m + 8 * g) = (f32x4){accu[m][4 * g], accu[m][4 * g + 1],
                                                  accu[m][4 * g + 2], accu[m][4 * g + 3]};
   }
-  if (a.pq_out) project_rows(accu, wPQ, biasPQ, a.pq_out + (size_t)nrow * PQW, nvalid, lane);
+  if (a.pq_out)
+    project_rows<P>(accu, wPQ, biasPQ, kPQ, a.pq_out + (size_t)nrow * PQW, nvalid, lane);
 }
 
-template <bool CENT>
+template <typename P, bool CENT>
 __global__ __launch_bounds__(FT) void conv_x3_kernel(Args a) {
+  constexpr int WE_OFF = Blk<P>::WE_OFF, W2_OFF = Blk<P>::W2_OFF, W_LDS = Blk<P>::W_LDS;
+  constexpr bool SC = P::SCALED;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  __shared__ float nrm[4];
+  __shared__ float nrm[6];
   if (threadIdx.x < 2) {
     nrm[2 * threadIdx.x] = *a.mu[threadIdx.x];
     nrm[2 * threadIdx.x + 1] = *a.sd[threadIdx.x];
+    nrm[4 + threadIdx.x] = threadIdx.x == 0 ? descale<P>(a.w[0], C, HID) : descale<P>(a.w[1], HID, C);
   }
-  stage_lds<FT>(lds + WE_OFF, a.w[0], x3_bytes(C, HID));
-  stage_lds<FT>(lds + W2_OFF, a.w[1], x3_bytes(HID, C));
+  stage_lds<FT>(lds + WE_OFF, a.w[0], P::image_bytes(C, HID));
+  stage_lds<FT>(lds + W2_OFF, a.w[1], P::image_bytes(HID, C));
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r = lane & 31, h = lane >> 5;
   float* T = (float*)(lds + W_LDS + wave * T_BYTES);  // [TR][TS] message rows
   const WLds wE{lds + WE_OFF + lane * 16, plane_bytes(C, HID)};
   const WLds w2{lds + W2_OFF + lane * 16, plane_bytes(HID, C)};
-  const float* bias2 = (const float*)(lds + W2_OFF + 3 * plane_bytes(HID, C));
+  const float* bias2 = (const float*)(lds + W2_OFF + P::NP * plane_bytes(HID, C));
   const float mu0 = nrm[0], sd0 = nrm[1], mu1 = nrm[2], sd1 = nrm[3];
+  const float ds0 = nrm[4], ds1 = nrm[5];  // 2^-s of W_e (P | Q arrive times 2^s_e) and of W_2
 
   // this XCD's share of the NBLK-node blocks: [xlo(xcd), xlo(xcd + 1))
   const int xcd = blockIdx.x % NXCD;
@@ -314,15 +353,15 @@ __global__ __launch_bounds__(FT) void conv_x3_kernel(Args a) {
         for (int g = 0; g < 4; ++g)
 #pragma unroll
           for (int t = 0; t < 4; ++t) acc1[m][4 * g + t] = rw.p[4 * m + g][t] + rw.q[4 * m + g][t];
-      layer_x3<4, 4, 4>(acc1, wE, 0, [&](int s) { return split8(rw.e[2 * s], rw.e[2 * s + 1]); });
+      layer_x3<4, 4, 4>(acc1, wE, 0, [&](int s) { return P::split(rw.e[2 * s], rw.e[2 * s + 1]); });
       // norm 1's statistics now; its scale + LeakyReLU inside layer 2's B operand
-      const Pend pn1 = pend_norm_leaky<4, CENT>(acc1, mu0, sd0);
+      const Pend pn1 = pend_norm_leaky<4, CENT, SC>(acc1, mu0, sd0, ds0);
       // ---- layer 2 (B operand = layer 1's accumulators)
       f32x16 acc2[2];
 #pragma unroll
       for (int m = 0; m < 2; ++m) acc2[m] = ld_bias_frag(bias2, m, h);
       layer_x3<8, 2, 2, 1>(acc2, w2, 0,
-                           [&](int s) { return split_acc_pend<1>(acc1[s >> 1], s & 1, pn1); });
+                           [&](int s) { return split_acc_pend<1, P>(acc1[s >> 1], s & 1, pn1); });
       // acc1 and this tile's rows are dead: the next tile's e rows go out now and arrive
       // behind norm 2 and the segmented sum (no registers beyond the rows' own)
       __builtin_amdgcn_sched_barrier(0);
@@ -332,7 +371,7 @@ __global__ __launch_bounds__(FT) void conv_x3_kernel(Args a) {
         dcur = d1;
         tile_idx(t0 + 64, p1, d1, s1);
       }
-      norm_leaky<2, CENT>(acc2, mu1, sd1);
+      norm_leaky<2, CENT, SC>(acc2, mu1, sd1, ds1);
       // ---- segmented sum in edge order, TR edges per LDS pass: a full pass runs without
       //      bounds checks, each edge one add and one select; a destination change (a set
       //      bit of smask, wave-uniform, ~2.5 per tile) flushes the finished sum to its row
@@ -399,50 +438,59 @@ __global__ __launch_bounds__(FT) void conv_x3_kernel(Args a) {
 // step; the aggregate rows come from the edge launch's scratch.  8 waves per workgroup, two
 // per SIMD (M: 12 waves 0.603 vs 0.600-0.603 ms per layer -- its time is the P | Q write
 // volume; 16 waves spill).
-static constexpr int NU_OFF = 0;
-static constexpr int NPQ_OFF = al16(x3_bytes(2 * C, C));
-static constexpr int NODE_LDS = NPQ_OFF + al16(x3_bytes(C, PQW));
 static constexpr int NFT = 512, NW_NODE = NFT / 64;
-static_assert(NODE_LDS <= DYN_LDS_MAX, "node_x3 LDS");
-template <bool CENT>
+template <typename P>
+struct Node {
+  static constexpr int NU_OFF = 0;
+  static constexpr int NPQ_OFF = al16(P::image_bytes(2 * C, C));
+  static constexpr int LDS = NPQ_OFF + al16(P::image_bytes(C, PQW));
+  static_assert(LDS <= DYN_LDS_MAX, "node_x3 LDS");
+};
+template <typename P, bool CENT>
 __global__ __launch_bounds__(NFT) void node_x3_kernel(Args a) {
+  constexpr int NU_OFF = Node<P>::NU_OFF, NPQ_OFF = Node<P>::NPQ_OFF;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  __shared__ float nrm[2];
+  __shared__ float nrm[4];
   if (threadIdx.x == 0) {
     nrm[0] = *a.mu[2];
     nrm[1] = *a.sd[2];
+    nrm[2] = descale<P>(a.w[2], 2 * C, C);
+    nrm[3] = a.wpq ? pq_rescale<P>(a.wpq, a.we_next) : 1.f;
   }
-  stage_lds<NFT>(lds + NU_OFF, a.w[2], x3_bytes(2 * C, C));
-  stage_lds<NFT>(lds + NPQ_OFF, a.wpq, a.wpq ? x3_bytes(C, PQW) : 0);
+  stage_lds<NFT>(lds + NU_OFF, a.w[2], P::image_bytes(2 * C, C));
+  stage_lds<NFT>(lds + NPQ_OFF, a.wpq, a.wpq ? P::image_bytes(C, PQW) : 0);
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const WLds wU{lds + NU_OFF + lane * 16, plane_bytes(2 * C, C)};
   const WLds wPQ{lds + NPQ_OFF + lane * 16, plane_bytes(C, PQW)};
-  const float* biasU = (const float*)(lds + NU_OFF + 3 * plane_bytes(2 * C, C));
-  const float* biasPQ = (const float*)(lds + NPQ_OFF + 3 * plane_bytes(C, PQW));
-  const float muU = nrm[0], sdU = nrm[1];
+  const float* biasU = (const float*)(lds + NU_OFF + P::NP * plane_bytes(2 * C, C));
+  const float* biasPQ = (const float*)(lds + NPQ_OFF + P::NP * plane_bytes(C, PQW));
+  const float muU = nrm[0], sdU = nrm[1], dsU = nrm[2], kPQ = nrm[3];
   const int ntiles = (a.n_nodes + 31) / 32;
   const int stride = gridDim.x * NW_NODE;
   for (int t = blockIdx.x * NW_NODE + wave; t < ntiles; t += stride) {
     NodeRows w;
     const int n0 = 32 * t, n1 = min(32 * t + 32, a.n_nodes);
     load_node_rows(a, n0, n1, lane, w);
-    node_compute<CENT>(a, w, n0, n1, wU, biasU, wPQ, biasPQ, muU, sdU, lane);
+    node_compute<P, CENT>(a, w, n0, n1, wU, biasU, wPQ, biasPQ, muU, sdU, dsU, kPQ, lane);
   }
 }
 
 // P | Q = W_pq x + [b1; 0] for dense float32 rows (the first layer's projections):
 // W_pq packed FAST_IN x3 (K = 64, N = 256), staged in LDS; one 32-row tile per wave
+// (we: the W_e image of the layer that will read the rows -- its scale, pq_rescale)
 static constexpr int PFT = 256;
+template <typename P>
 __global__ __launch_bounds__(PFT) void proj_x3_kernel(const float* x, int ldx, int n_nodes,
-                                                      const char* wpq, float* pq) {
+                                                      const char* wpq, const char* we, float* pq) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  constexpr int NB = x3_bytes(C, PQW);
+  constexpr int NB = P::image_bytes(C, PQW);
+  const float k = pq_rescale<P>(wpq, we);
   stage_lds<PFT>(lds, wpq, NB);
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r = lane & 31, h = lane >> 5;
-  const float* bias = (const float*)(lds + 3 * plane_bytes(C, PQW));
+  const float* bias = (const float*)(lds + P::NP * plane_bytes(C, PQW));
   const long ntiles = (n_nodes + 31) / 32;
   for (long t = (long)blockIdx.x * (PFT / 64) + wave; t < ntiles; t += (long)gridDim.x * (PFT / 64)) {
     const long row = t * 32 + r;
@@ -459,7 +507,12 @@ __global__ __launch_bounds__(PFT) void proj_x3_kernel(const float* x, int ldx, i
       f32x16 acc[4];
 #pragma unroll
       for (int m = 0; m < 4; ++m) acc[m] = ld_bias_frag(bias, 4 * half + m, h);
-      layer_x3<4, 4, 8>(acc, WLds{lds + lane * 16, plane_bytes(C, PQW)}, 4 * half, [&](int s) { return split8(xb[s][0], xb[s][1]); });
+      layer_x3<4, 4, 8>(acc, WLds{lds + lane * 16, plane_bytes(C, PQW)}, 4 * half,
+                        [&](int s) { return P::split(xb[s][0], xb[s][1]); });
+      if constexpr (P::SCALED) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc[m] *= k;
+      }
       if (valid) {
         float* po = pq + (size_t)row * PQW + 128 * half + 4 * h;
 #pragma unroll
@@ -495,17 +548,20 @@ __global__ __launch_bounds__(PFT) void proj_x3_kernel(const float* x, int ldx, i
 // workspace; XCD-major ranks, so an XCD's waves hold one contiguous node range), walked in
 // 32-edge tiles that may span destinations -- each destination's messages are still summed
 // in CSR order by one wave, the running sum carried from tile to tile.
+// Under h2 the same program runs over half the MFMAs: a tile-by-tile sub-chunk carries the
+// three products of its M-tile, and the product-by-product k-steps have three sub-chunks
+// instead of six, each taking the vector work of two of b3's (sub_prod below); the splits
+// are 16 instead of 44 instructions per k-step, so the vector work per MFMA about doubles
+// and the interleave ratios with it.
 // Registers: the weight fragments are read from LDS into AGPRs (inline ds_read, the MFMA
 // takes its A operand from AGPRs), the rest stays in VGPRs (256 + ~110 AGPRs, no scratch).
-// LDS: the W_e and W_2 planes (96 KiB), layer 2's bias, and per wave the message transpose
+// LDS: the W_e and W_2 planes (b3 96 KiB, h2 64 KiB), layer 2's bias, and per wave the message transpose
 // tile and a ring of the P rows of its last 8 destinations (a tile's P[dst] is one row per
 // destination: 2 rows loaded per tile instead of one row per edge).
 typedef float f32x32 __attribute__((ext_vector_type(32)));
 namespace sp {
 constexpr int FT = 256, NW = FT / 64;
 constexpr int PLE = plane_bytes(C, HID), PL2 = plane_bytes(HID, C);  // 16 KiB each
-constexpr int OFF_W2 = 3 * PLE;
-constexpr int OFF_BUF = OFF_W2 + 3 * PL2;
 constexpr int TS2 = 68;            // message transpose: row stride (floats)
 constexpr int TBUF = 32 * TS2 * 4;  // per wave: one tile's messages while transposing
 constexpr int RING = 8;             // per wave: P rows of the last RING destinations (slot = node & 7)
@@ -517,10 +573,15 @@ constexpr int RING = 8;             // per wave: P rows of the last RING destina
 #endif
 constexpr int RS = HID + RG_SP_RING_PAD;
 constexpr int BUF = TBUF + RING * RS * 4;
-constexpr int OFF_BIAS = OFF_BUF + NW * BUF;  // layer 2's bias, accumulator order
-constexpr int OFF_NZ = OFF_BIAS + C * 4;       // a row of -0.0: the "P" of a slow-path tile
-constexpr int LDS = OFF_NZ + HID * 4;
-static_assert(LDS <= 160 * 1024, "conv_x3_sp LDS");
+template <typename P>
+struct Lay {  // the LDS layout under scheme P
+  static constexpr int OFF_W2 = P::NP * PLE;
+  static constexpr int OFF_BUF = OFF_W2 + P::NP * PL2;
+  static constexpr int OFF_BIAS = OFF_BUF + NW * BUF;  // layer 2's bias, accumulator order
+  static constexpr int OFF_NZ = OFF_BIAS + C * 4;       // a row of -0.0: the "P" of a slow-path tile
+  static constexpr int LDS = OFF_NZ + HID * 4;
+  static_assert(LDS <= 160 * 1024, "conv_x3_sp LDS");
+};
 constexpr int GMAX = 256;          // workgroups (one per CU)
 constexpr int WMAX = GMAX * NW;    // waves
 constexpr int SMAX = 8;            // slabs: the table holds WMAX * SMAX + 1 node boundaries
@@ -529,9 +590,9 @@ constexpr int SMAX = 8;            // slabs: the table holds WMAX * SMAX + 1 nod
 __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)p; }
 // one weight fragment LDS -> AGPRs (the MFMA reads its A operand from there); completion is
 // not tracked by the compiler: wait_frags before use
-template <int OFF>
-__device__ __forceinline__ bf16x8_t dsa(uint32_t a) {
-  bf16x8_t r;
+template <typename V, int OFF>
+__device__ __forceinline__ V dsa(uint32_t a) {
+  V r;
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(r) : "v"(a), "i"(OFF));
   return r;
 }
@@ -540,84 +601,84 @@ __device__ __forceinline__ bf16x8_t dsa(uint32_t a) {
 // inline asm: the compiler's own counter model then knows every older LDS read is done (its
 // later waits for its own reads never stall on the untracked fragment reads issued after)
 __device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xc07f); }  // lgkmcnt(0)
-template <int N>
-__device__ __forceinline__ void wait_frags(bf16x8_t (&f)[N][3]);
-template <>
-__device__ __forceinline__ void wait_frags<4>(bf16x8_t (&f)[4][3]) {
+template <typename V>
+__device__ __forceinline__ void wait_frags(V (&f)[4][3]) {
   wait_lgkm0();
   asm volatile(""
                : "+a"(f[0][0]), "+a"(f[0][1]), "+a"(f[0][2]), "+a"(f[1][0]), "+a"(f[1][1]),
                  "+a"(f[1][2]), "+a"(f[2][0]), "+a"(f[2][1]), "+a"(f[2][2]), "+a"(f[3][0]),
                  "+a"(f[3][1]), "+a"(f[3][2]));
 }
-template <>
-__device__ __forceinline__ void wait_frags<2>(bf16x8_t (&f)[2][3]) {
+template <typename V>
+__device__ __forceinline__ void wait_frags(V (&f)[2][3]) {
   wait_lgkm0();
   asm volatile("" : "+a"(f[0][0]), "+a"(f[0][1]), "+a"(f[0][2]), "+a"(f[1][0]), "+a"(f[1][1]),
                     "+a"(f[1][2]));
 }
-// layer 1's A fragments of k-step S (W_e FAST_IN x3: K = 64, four M-tiles)
-template <int S>
-__device__ __forceinline__ void lda1(uint32_t b, bf16x8_t (&f)[4][3]) {
-#define RG_SP_L1(M, P) f[M][P] = dsa<P * sp::PLE + (M * 4 + S) * 1024>(b)
-  RG_SP_L1(0, 0); RG_SP_L1(0, 1); RG_SP_L1(0, 2); RG_SP_L1(1, 0); RG_SP_L1(1, 1); RG_SP_L1(1, 2);
-  RG_SP_L1(2, 0); RG_SP_L1(2, 1); RG_SP_L1(2, 2); RG_SP_L1(3, 0); RG_SP_L1(3, 1); RG_SP_L1(3, 2);
+template <typename V>
+__device__ __forceinline__ void wait_frags(V (&f)[4][2]) {
+  wait_lgkm0();
+  asm volatile("" : "+a"(f[0][0]), "+a"(f[0][1]), "+a"(f[1][0]), "+a"(f[1][1]), "+a"(f[2][0]),
+                    "+a"(f[2][1]), "+a"(f[3][0]), "+a"(f[3][1]));
+}
+template <typename V>
+__device__ __forceinline__ void wait_frags(V (&f)[2][2]) {
+  wait_lgkm0();
+  asm volatile("" : "+a"(f[0][0]), "+a"(f[0][1]), "+a"(f[1][0]), "+a"(f[1][1]));
+}
+// layer 1's A fragments of k-step S (W_e FAST_IN: K = 64, four M-tiles), every plane
+template <typename P, int S>
+__device__ __forceinline__ void lda1(uint32_t b, typename P::vec (&f)[4][P::NP]) {
+#define RG_SP_L1(M, PL) f[M][PL] = dsa<typename P::vec, PL * sp::PLE + (M * 4 + S) * 1024>(b)
+#define RG_SP_L1M(M)                           \
+  RG_SP_L1(M, 0);                              \
+  RG_SP_L1(M, 1);                              \
+  if constexpr (P::NP == 3) RG_SP_L1(M, 2)
+  RG_SP_L1M(0); RG_SP_L1M(1); RG_SP_L1M(2); RG_SP_L1M(3);
+#undef RG_SP_L1M
 #undef RG_SP_L1
 }
-// layer 2's A fragments of k-step S (W_2 FAST_CHAIN x3: K = 128, two M-tiles); b = W_2's base
-template <int S>
-__device__ __forceinline__ void lda2(uint32_t b, bf16x8_t (&f)[2][3]) {
-#define RG_SP_L2(M, P) f[M][P] = dsa<P * sp::PL2 + (M * 8 + S) * 1024>(b)
-  RG_SP_L2(0, 0); RG_SP_L2(0, 1); RG_SP_L2(0, 2); RG_SP_L2(1, 0); RG_SP_L2(1, 1); RG_SP_L2(1, 2);
+// layer 2's A fragments of k-step S (W_2 FAST_CHAIN: K = 128, two M-tiles); b = W_2's base
+template <typename P, int S>
+__device__ __forceinline__ void lda2(uint32_t b, typename P::vec (&f)[2][P::NP]) {
+#define RG_SP_L2(M, PL) f[M][PL] = dsa<typename P::vec, PL * sp::PL2 + (M * 8 + S) * 1024>(b)
+#define RG_SP_L2M(M)                           \
+  RG_SP_L2(M, 0);                              \
+  RG_SP_L2(M, 1);                              \
+  if constexpr (P::NP == 3) RG_SP_L2(M, 2)
+  RG_SP_L2M(0); RG_SP_L2M(1);
+#undef RG_SP_L2M
 #undef RG_SP_L2
 }
-// the six products of one k-step (weights of term <= 2, small terms first: layer_x3's order)
-// for M-tiles [0, MT); MMAJOR: tile by tile (its result complete early), else product-major
-template <int MT, bool MMAJOR>
-__device__ __forceinline__ void x3_step(f32x16 (&acc)[MT], const bf16x8_t (&A)[MT][3], const X3& b) {
+// the products of one k-step (small terms first: layer_x3's order per accumulator) for
+// M-tiles [0, MT); MMAJOR: tile by tile (its result complete early), else product-major
+template <typename P, int MT, bool MMAJOR>
+__device__ __forceinline__ void x3_step(f32x16 (&acc)[MT], const typename P::vec (&A)[MT][P::NP],
+                                        const typename P::terms& b) {
   if constexpr (MMAJOR) {
 #pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      acc[m] = mf(A[m][2], b.p0, acc[m]);
-      acc[m] = mf(A[m][1], b.p1, acc[m]);
-      acc[m] = mf(A[m][0], b.p2, acc[m]);
-      acc[m] = mf(A[m][1], b.p0, acc[m]);
-      acc[m] = mf(A[m][0], b.p1, acc[m]);
-      acc[m] = mf(A[m][0], b.p0, acc[m]);
-    }
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int i = 0; i < P::NPROD; ++i)
+        acc[m] = P::mfma(A[m][P::wp(i)], P::term(b, P::bp(i)), acc[m]);
   } else {
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = mf(A[m][2], b.p0, acc[m]);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = mf(A[m][1], b.p1, acc[m]);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = mf(A[m][0], b.p2, acc[m]);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = mf(A[m][1], b.p0, acc[m]);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = mf(A[m][0], b.p1, acc[m]);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = mf(A[m][0], b.p0, acc[m]);
+    products<P, MT>(acc, A, b);
   }
 }
-// one product of a k-step (x3_step's order: P = 0 .. 5) on every M-tile
-template <int P, int MT>
-__device__ __forceinline__ void x3_prod(f32x16 (&acc)[MT], const bf16x8_t (&A)[MT][3], const X3& b) {
-  constexpr int ia = P == 0 ? 2 : (P == 1 || P == 3) ? 1 : 0;
-  constexpr int ib = (P == 0 || P == 3 || P == 5) ? 0 : (P == 1 || P == 4) ? 1 : 2;
-  const bf16x8_t bb = ib == 0 ? b.p0 : ib == 1 ? b.p1 : b.p2;
+// one product of a k-step (the scheme's order: I = 0 .. NPROD - 1) on every M-tile
+template <typename P, int I, int MT>
+__device__ __forceinline__ void x3_prod(f32x16 (&acc)[MT], const typename P::vec (&A)[MT][P::NP],
+                                        const typename P::terms& b) {
+  const typename P::vec bb = P::term(b, P::bp(I));
 #pragma unroll
-  for (int m = 0; m < MT; ++m) acc[m] = mf(A[m][ia], bb, acc[m]);
+  for (int m = 0; m < MT; ++m) acc[m] = P::mfma(A[m][P::wp(I)], bb, acc[m]);
 }
-// the six products of a k-step on M-tile M alone (the same order per accumulator)
-template <int M, int MT>
-__device__ __forceinline__ void x3_tile(f32x16 (&acc)[MT], const bf16x8_t (&A)[MT][3], const X3& b) {
-  acc[M] = mf(A[M][2], b.p0, acc[M]);
-  acc[M] = mf(A[M][1], b.p1, acc[M]);
-  acc[M] = mf(A[M][0], b.p2, acc[M]);
-  acc[M] = mf(A[M][1], b.p0, acc[M]);
-  acc[M] = mf(A[M][0], b.p1, acc[M]);
-  acc[M] = mf(A[M][0], b.p0, acc[M]);
+// the products of a k-step on M-tile M alone (the same order per accumulator)
+template <typename P, int M, int MT>
+__device__ __forceinline__ void x3_tile(f32x16 (&acc)[MT], const typename P::vec (&A)[MT][P::NP],
+                                        const typename P::terms& b) {
+#pragma unroll
+  for (int i = 0; i < P::NPROD; ++i) acc[M] = P::mfma(A[M][P::wp(i)], P::term(b, P::bp(i)), acc[M]);
 }
 // keeps a value computed where it stands (IR sinking would otherwise move work whose only
 // use lies past a branch into the block after it, out of the sub-chunk it was placed in)
@@ -649,11 +710,13 @@ __device__ __forceinline__ void sq_partial(const f32x16& t, float (&u)[8], bool 
 }
 // channel_normalization's scale from the partial sums of a CENTRED layer of N features
 // (row_inv_std<MT, true>): 0.505 sd / (std + eps), the LeakyReLU prescale folded in
-template <int N>
-__device__ __forceinline__ Pend finish_norm(const float (&u)[8], float mu, float sd) {
+// SC: the sums are of pre-activations times 2^s and ds = 2^-s (row_inv_std's scaled form)
+template <int N, bool SC>
+__device__ __forceinline__ Pend finish_norm(const float (&u)[8], float mu, float sd, float ds) {
   const float ss = add_xor32(((u[0] + u[1]) + (u[2] + u[3])) + ((u[4] + u[5]) + (u[6] + u[7])));
-  const float inv =
-      __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(ss * (1.f / (float)(N - 1))) + X3_NORM_EPS);
+  const float sdev = __builtin_amdgcn_sqrtf(ss * (1.f / (float)(N - 1)));
+  const float inv = SC ? ds * __builtin_amdgcn_rcpf(fmaf(sdev, ds, X3_NORM_EPS))
+                       : __builtin_amdgcn_rcpf(sdev + X3_NORM_EPS);
   return Pend{X3_LEAKY_PRE * (sd * inv), X3_LEAKY_PRE * mu};
 }
 
@@ -672,15 +735,45 @@ __device__ unsigned long long g_sp_stamp[16];
 #define SP_STAMP(i) do {} while (0)
 #endif
 
-template <bool CENT>
+// `n` groups of one MFMA and the vector work beside it under either scheme: V6 VALU (M6
+// vector-memory instructions every other group) under b3; under h2 the same vector work
+// stands beside half as many MFMAs, so each group takes twice as much
+template <typename P, int N, int V6, int M6 = 0>
+__device__ __forceinline__ void beside() {
+  if constexpr (P::NPROD == 6) interleave<N, V6, M6>();
+  else interleave<N / 2, 2 * V6, N % 4 == 0 ? 2 * M6 : (3 * M6 + 1) / 2>();
+}
+// one product-by-product sub-chunk: b3's sub-chunk I = product I of the k-step on its MT
+// M-tiles with V6 VALU beside each MFMA; under h2 sub-chunks 2 i and 2 i + 1 are ONE
+// sub-chunk around product i (the vector work placed before an even I simply joins the next
+// odd one's), V3 VALU beside each MFMA
+template <typename P, int I, int V6, int V3, int M6 = 0, int MT>
+__device__ __forceinline__ void sub_prod(f32x16 (&acc)[MT], const typename P::vec (&A)[MT][P::NP],
+                                         const typename P::terms& b) {
+  if constexpr (P::NPROD == 6) {
+    x3_prod<P, I>(acc, A, b);
+    interleave<MT, V6, M6>();
+    fence();
+  } else if constexpr (I % 2 == 1) {
+    x3_prod<P, I / 2>(acc, A, b);
+    interleave<MT, V3, M6>();
+    fence();
+  }
+}
+
+template <typename P, bool CENT>
 __global__ __launch_bounds__(sp::FT) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
   static_assert(CENT, "the one-wave edge launch takes centred layers");
+  typedef sp::Lay<P> L;
+  typedef typename P::terms Terms;
+  typedef typename P::vec Vec;
+  constexpr bool SC = P::SCALED;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  stage_lds<sp::FT>(lds, a.w[0], 3 * sp::PLE);
-  stage_lds<sp::FT>(lds + sp::OFF_W2, a.w[1], 3 * sp::PL2);
-  stage_lds<sp::FT>(lds + sp::OFF_BIAS, a.w[1] + 3 * sp::PL2, C * 4);
-  if (threadIdx.x < HID) ((float*)(lds + sp::OFF_NZ))[threadIdx.x] = -0.f;
+  stage_lds<sp::FT>(lds, a.w[0], P::NP * sp::PLE);
+  stage_lds<sp::FT>(lds + L::OFF_W2, a.w[1], P::NP * sp::PL2);
+  stage_lds<sp::FT>(lds + L::OFF_BIAS, a.w[1] + P::NP * sp::PL2, C * 4);
+  if (threadIdx.x < HID) ((float*)(lds + L::OFF_NZ))[threadIdx.x] = -0.f;
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r = lane & 31, h = lane >> 5;
@@ -708,11 +801,14 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
   const int T = (V + 31) >> 5;
   if (T <= 0) return;
   const float mu0 = *a.mu[0], sd0 = *a.sd[0], mu1 = *a.mu[1], sd1 = *a.sd[1];
-  const float* bias2 = (const float*)(lds + sp::OFF_BIAS);  // layer 2's bias
+  // 2^-s of W_e -- the P | Q rows arrive times its 2^s, so layer 1's accumulators are the
+  // pre-activations times 2^s from their first add -- and of W_2 (its bias is packed times 2^s)
+  const float ds0 = descale<P>(a.w[0], C, HID), ds1 = descale<P>(a.w[1], HID, C);
+  const float* bias2 = (const float*)(lds + L::OFF_BIAS);  // layer 2's bias
   const uint32_t lb = lds_addr(lds);
   const uint32_t aw = lb + lane * 16;  // + the fragment's immediate offset
-  const uint32_t aw2 = aw + sp::OFF_W2;
-  char* bufp = lds + sp::OFF_BUF + wave * sp::BUF;
+  const uint32_t aw2 = aw + L::OFF_W2;
+  char* bufp = lds + L::OFF_BUF + wave * sp::BUF;
   float* Tm = (float*)bufp;  // [32][TS2] message rows while transposing
 
   // ---- per-tile inputs
@@ -767,7 +863,7 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
   // adds nothing (q + -0 = q, signed zeros included), so no ring row of another node
   // reaches the sum
   bool fast = false;  // tile 0's P is in qn
-  const float* nzrow = (const float*)(lds + sp::OFF_NZ);
+  const float* nzrow = (const float*)(lds + L::OFF_NZ);
   auto ring_p = [&](int d, int m, f32x4 (&p)[4]) {  // M-tile m of P[d] from the ring
     const float* rp = (fast ? ring + (d & (sp::RING - 1)) * sp::RS : nzrow) + 4 * h + 32 * m;
 #pragma unroll
@@ -891,7 +987,7 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
   init_tile(d0, qn, acc1[0], 0);
   f32x4 pr[4];  // the ring rows of the next M-tile to initialise, read one sub-chunk ahead
   ring_p(d0, 1, pr);
-  X3 b1 = split8(en[0], en[1]);
+  Terms b1 = P::split(en[0], en[1]);
   uint32_t mask_c = tile_mask(0, d0, a.n_nodes);
   int d_c = d0;
   // the previous tile's state (none yet: no mask bits, zero messages)
@@ -905,8 +1001,8 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
   float run = 0.f;       // lane = feature: the running sum carried into the previous tile
   f32x32 rv;             // the previous tile's running sums
   int crow = a.n_nodes;  // the destination row of `run` (a dummy row before the first)
-  bf16x8_t A1[2][4][3], A2[2][2][3];
-  lda1<0>(aw, A1[0]);
+  Vec A1[2][4][P::NP], A2[2][2][P::NP];
+  lda1<P, 0>(aw, A1[0]);
 #if RG_CX3_SP_STAMP
   unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long st_last = __builtin_amdgcn_s_memtime();
@@ -924,106 +1020,86 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
     // the flushes, the transposes -- without any beside them)
     // ======== A0: k-step 0 tile by tile; beside M-tile m the P + Q init of M-tile m + 1;
     //          the split of k-step 1; norm 2's statistics of tile t - 1
-    wait_frags<4>(A1[0]);
-    lda1<1>(aw, A1[1]);
-    X3 b1n = split8(ev[2], ev[3]);
+    wait_frags(A1[0]);
+    lda1<P, 1>(aw, A1[1]);
+    Terms b1n = P::split(ev[2], ev[3]);
     init_from(pr, qn, acc1[1], 1);
     ring_p(d_c, 2, pr);
-    x3_tile<0>(acc1, A1[0], b1);
-    interleave<6, 5>();
+    x3_tile<P, 0>(acc1, A1[0], b1);
+    beside<P, 6, 5>();
     fence();
     float u2[8];
     init_from(pr, qn, acc1[2], 2);
     ring_p(d_c, 3, pr);
     sq_partial(acc2p[0], u2, true);
-    x3_tile<1>(acc1, A1[0], b1);
-    interleave<6, 6>();
+    x3_tile<P, 1>(acc1, A1[0], b1);
+    beside<P, 6, 6>();
     fence();
     init_from(pr, qn, acc1[3], 3);
     sq_partial(acc2p[1], u2, false);
-    x3_tile<2>(acc1, A1[0], b1);
-    interleave<6, 6>();
+    x3_tile<P, 2>(acc1, A1[0], b1);
+    beside<P, 6, 6>();
     fence();
-    const Pend pn2 = finish_norm<C>(u2, mu1, sd1);
-    x3_tile<3>(acc1, A1[0], b1);
-    interleave<6, 4>();
+    const Pend pn2 = finish_norm<C, SC>(u2, mu1, sd1, ds1);
+    x3_tile<P, 3>(acc1, A1[0], b1);
+    beside<P, 6, 4>();
     fence();
     SP_STAMP(7);  // A0
     // ======== A1: k-step 1 product by product; the split of k-step 2; tile t - 1: norm 2's
     //          scale + LeakyReLU, its message rows to the buffer and its columns back (one
     //          wave's LDS operations complete in order: no wait between them)
-    wait_frags<4>(A1[1]);
-    lda1<2>(aw, A1[0]);
-    b1 = split8(ev[4], ev[5]);
+    wait_frags(A1[1]);
+    lda1<P, 2>(aw, A1[0]);
+    b1 = P::split(ev[4], ev[5]);
     norm2_apply(acc2p[0], pn2, 0, 4);
-    x3_prod<0>(acc1, A1[1], b1n);
-    interleave<4, 5>();
-    fence();
+    sub_prod<P, 0, 5, 8>(acc1, A1[1], b1n);
     norm2_apply(acc2p[0], pn2, 4, 12);
-    x3_prod<1>(acc1, A1[1], b1n);
-    interleave<4, 4>();
-    fence();
+    sub_prod<P, 1, 4, 8>(acc1, A1[1], b1n);
     norm2_apply(acc2p[0], pn2, 12, 16);
     write_msg(acc2p[0], 0);
-    x3_prod<2>(acc1, A1[1], b1n);
-    interleave<4, 4>();
-    fence();
+    sub_prod<P, 2, 4, 8>(acc1, A1[1], b1n);
     norm2_apply(acc2p[1], pn2, 0, 8);
-    x3_prod<3>(acc1, A1[1], b1n);
-    interleave<4, 4>();
-    fence();
+    sub_prod<P, 3, 4, 8>(acc1, A1[1], b1n);
     norm2_apply(acc2p[1], pn2, 8, 16);
-    x3_prod<4>(acc1, A1[1], b1n);
-    interleave<4, 4>();
-    fence();
+    sub_prod<P, 4, 4, 6>(acc1, A1[1], b1n);
     write_msg(acc2p[1], 1);
 #pragma unroll
     for (int j = 0; j < 32; ++j) cv[j] = Tm[j * sp::TS2 + lane];
-    x3_prod<5>(acc1, A1[1], b1n);
-    interleave<4, 2>();
-    fence();
+    sub_prod<P, 5, 2, 6>(acc1, A1[1], b1n);
     SP_STAMP(8);  // A1
     // ======== A2: k-step 2 product by product; the split of k-step 3; tile t - 1's running
     //          sums; tile t + 1's e rows
-    wait_frags<4>(A1[0]);
-    lda1<3>(aw, A1[1]);
-    b1n = split8(ev[6], ev[7]);
+    wait_frags(A1[0]);
+    lda1<P, 3>(aw, A1[1]);
+    b1n = P::split(ev[6], ev[7]);
     uint32_t kb[32];
     keeps(0, 16, mask_p, kb);
-    x3_prod<0>(acc1, A1[0], b1);
-    interleave<4, 3>();
-    fence();
+    sub_prod<P, 0, 3, 5>(acc1, A1[0], b1);
     const float run_in = run;
     float prev = run_in;
     keeps(16, 32, mask_p, kb);
     scan_part(0, 8, cv, kb, prev, rv);
-    x3_prod<1>(acc1, A1[0], b1);
-    interleave<4, 2>();
-    fence();
+    sub_prod<P, 1, 2, 5>(acc1, A1[0], b1);
     scan_part(8, 16, cv, kb, prev, rv);
-    x3_prod<2>(acc1, A1[0], b1);
-    interleave<4, 2>();
-    fence();
+    sub_prod<P, 2, 2, 4>(acc1, A1[0], b1);
     scan_part(16, 24, cv, kb, prev, rv);
-    x3_prod<3>(acc1, A1[0], b1);
-    interleave<4, 2>();
-    fence();
+    sub_prod<P, 3, 2, 4>(acc1, A1[0], b1);
     scan_part(24, 32, cv, kb, prev, rv);
-    x3_prod<4>(acc1, A1[0], b1);
-    interleave<4, 2>();
-    fence();
+    sub_prod<P, 4, 2, 0>(acc1, A1[0], b1);
     load_e(q_nn, en);
-    x3_prod<5>(acc1, A1[0], b1);
-    interleave<4, 0, 2>();
-    fence();
+    if constexpr (P::NPROD == 6) {
+      sub_prod<P, 5, 0, 0, 2>(acc1, A1[0], b1);
+    } else {
+      sub_prod<P, 5, 0, 2, 4>(acc1, A1[0], b1);
+    }
     SP_STAMP(9);  // A2
     // ======== A3: k-step 3 tile by tile (norm 1's partial sums follow one tile behind);
     //          tile t - 1's first four finished destinations, one per sub-chunk; tile t + 1's
     //          Q rows and ring rows, the indices of tile t + 2 (a one-wave SIMD pays each
     //          vector-memory instruction's issue in its own stream, so the loads are spread
     //          over the sub-chunks)
-    wait_frags<4>(A1[1]);
-    lda2<0>(aw2, A2[0]);
+    wait_frags(A1[1]);
+    lda2<P, 0>(aw2, A2[0]);
     uint32_t mask_rest = mask_p;
     const int dl_c = __builtin_amdgcn_readlane(d_c, 31);   // tile t's last destination
     const int dl_n = __builtin_amdgcn_readlane(d_nn, 31);  // tile t + 1's
@@ -1031,31 +1107,31 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
     const int d_3 = a.dst[q_3], s_3 = a.src[q_3];
     load_q_part(s_nn, qn, 0, 6);
     flush_slot(mask_rest, rv, run_in, d_p, crow);
-    x3_tile<0>(acc1, A1[1], b1n);
-    interleave<6, 4, 2>();
+    x3_tile<P, 0>(acc1, A1[1], b1n);
+    beside<P, 6, 4, 2>();
     fence();
     SP_STAMP(10);  // A3.0
     float u1[8];
     load_q_part(s_nn, qn, 6, 12);
     flush_slot(mask_rest, rv, run_in, d_p, crow);
     sq_partial(acc1[0], u1, true);
-    x3_tile<1>(acc1, A1[1], b1n);
-    interleave<6, 6, 2>();
+    x3_tile<P, 1>(acc1, A1[1], b1n);
+    beside<P, 6, 6, 2>();
     fence();
     SP_STAMP(11);  // A3.1
     load_q_part(s_nn, qn, 12, 16);
     ring_load(dl_n, rp);
     flush_slot(mask_rest, rv, run_in, d_p, crow);
     sq_partial(acc1[1], u1, false);
-    x3_tile<2>(acc1, A1[1], b1n);
-    interleave<6, 6, 2>();
+    x3_tile<P, 2>(acc1, A1[1], b1n);
+    beside<P, 6, 6, 2>();
     fence();
     SP_STAMP(14);  // A3.2
     flush_slot(mask_rest, rv, run_in, d_p, crow);
     sq_partial(acc1[2], u1, false);
     pin(u1);
-    x3_tile<3>(acc1, A1[1], b1n);
-    interleave<6, 6>();
+    x3_tile<P, 3>(acc1, A1[1], b1n);
+    beside<P, 6, 6>();
     fence();
     SP_STAMP(1);  // region A
     // the slow path: more than four new destinations in tile t + 1 (never on a kNN graph of
@@ -1074,7 +1150,7 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
     flush(mask_rest, rv, run_in, d_p, crow);
     run = rv[31];
     sq_partial(acc1[3], u1, false);
-    const Pend pn1 = finish_norm<HID>(u1, mu0, sd0);
+    const Pend pn1 = finish_norm<HID, SC>(u1, mu0, sd0, ds0);
     f32x16 acc2[2] = {ld_bias_frag(bias2, 0, h), ld_bias_frag(bias2, 1, h)};
     fence();
     SP_STAMP(2);  // region B
@@ -1083,23 +1159,30 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
     //          beside k-step 6 its first accumulator tile (acc1[0] is dead after k-step 1's
     //          split; its ring rows read one k-step ahead), beside k-step 7 its first B
     //          operand
-    X3 b2 = split_acc_pend<1>(acc1[0], 0, pn1);
-    X3 b2n;
+    Terms b2 = split_acc_pend<1, P>(acc1[0], 0, pn1);
+    Terms b2n;
     // the next k-step's fragment reads right behind the chunk's first product (two MFMAs):
     // issued later in the chunk they are still in flight at the next chunk's wait
+    // the products after a k-step's first, on both M-tiles (b3: ten MFMAs, h2: four)
+    auto rest2 = [&](const Vec (&A)[2][P::NP], const Terms& b) {
+      x3_prod<P, 1>(acc2, A, b);
+      x3_prod<P, 2>(acc2, A, b);
+      if constexpr (P::NPROD == 6) {
+        x3_prod<P, 3>(acc2, A, b);
+        x3_prod<P, 4>(acc2, A, b);
+        x3_prod<P, 5>(acc2, A, b);
+      }
+    };
 #define RG_SP_C(S, BUFI, NEXT, EXTRA)                                  \
-    wait_frags<2>(A2[BUFI]);                                           \
-    x3_prod<0>(acc2, A2[BUFI], S % 2 ? b2n : b2);                      \
-    lda2<S + 1>(aw2, A2[BUFI ^ 1]);                                     \
+    wait_frags(A2[BUFI]);                                              \
+    x3_prod<P, 0>(acc2, A2[BUFI], S % 2 ? b2n : b2);                   \
+    lda2<P, S + 1>(aw2, A2[BUFI ^ 1]);                                  \
     fence();                                                           \
-    NEXT = split_acc_pend<1>(acc1[(S + 1) >> 1], (S + 1) & 1, pn1);    \
+    NEXT = split_acc_pend<1, P>(acc1[(S + 1) >> 1], (S + 1) & 1, pn1); \
     EXTRA;                                                             \
-    x3_prod<1>(acc2, A2[BUFI], S % 2 ? b2n : b2);                      \
-    x3_prod<2>(acc2, A2[BUFI], S % 2 ? b2n : b2);                      \
-    x3_prod<3>(acc2, A2[BUFI], S % 2 ? b2n : b2);                      \
-    x3_prod<4>(acc2, A2[BUFI], S % 2 ? b2n : b2);                      \
-    x3_prod<5>(acc2, A2[BUFI], S % 2 ? b2n : b2);                      \
-    interleave<10, 6>();                                               \
+    rest2(A2[BUFI], S % 2 ? b2n : b2);                                 \
+    if constexpr (P::NPROD == 6) interleave<10, 6>();                  \
+    else interleave<4, 9>();                                           \
     fence();
     RG_SP_C(0, 0, b2n, (void)0)
     RG_SP_C(1, 1, b2, (void)0)
@@ -1110,19 +1193,16 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
     RG_SP_C(6, 0, b2n, init_from(pr, qn, acc1[0], 0))
 #undef RG_SP_C
     SP_STAMP(3);  // C0 - C6
-    wait_frags<2>(A2[1]);
-    x3_prod<0>(acc2, A2[1], b2n);
-    lda1<0>(aw, A1[0]);  // the next tile's first layer-1 fragments
+    wait_frags(A2[1]);
+    x3_prod<P, 0>(acc2, A2[1], b2n);
+    lda1<P, 0>(aw, A1[0]);  // the next tile's first layer-1 fragments
     fence();
-    b1 = split8(en[0], en[1]);
-    x3_prod<1>(acc2, A2[1], b2n);
-    x3_prod<2>(acc2, A2[1], b2n);
-    x3_prod<3>(acc2, A2[1], b2n);
-    x3_prod<4>(acc2, A2[1], b2n);
-    x3_prod<5>(acc2, A2[1], b2n);
+    b1 = P::split(en[0], en[1]);
+    rest2(A2[1], b2n);
     ring_p(d_nn, 1, pr);
     const uint32_t mask_n = tile_mask(t + 1, d_nn, dl_c);
-    interleave<12, 2>();
+    if constexpr (P::NPROD == 6) interleave<12, 2>();
+    else interleave<4, 6>();
     fence();
     SP_STAMP(5);  // C7
     // rotate the pipeline
@@ -1140,7 +1220,7 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
   //      the destination of the range's last edge (edges past it carry no bit and are not
   //      counted: the sum after edge nv - 1)
   wait_lgkm0();
-  norm_leaky<2, CENT>(acc2p, mu1, sd1);
+  norm_leaky<2, CENT, SC>(acc2p, mu1, sd1, ds1);
   write_msgs(acc2p);
   wait_lgkm0();
   float cv[32];
@@ -1211,21 +1291,40 @@ extern "C" size_t rg_conv_layer_x3_workspace_size(int n_nodes) {
   return CTR_BYTES + x3_agg_bytes(n_nodes) + (size_t)(sp::WMAX * sp::SMAX + 1) * sizeof(int);
 }
 
-extern "C" int rg_conv_proj_x3(const rg_layer* pq, const float* x, int ldx, int n_nodes,
-                               float* pq_out, void* stream) {
-  RG_REQUIRE(pq && pq->in_dim == C && pq->out_dim == PQW && !pq->norm_mu && pq->act == RG_ACT_NONE,
-             RG_ERR_UNSUPPORTED, "rg_conv_proj_x3: expects the 64 -> 256 projection");
-  RG_REQUIRE(ldx % 4 == 0, RG_ERR_UNSUPPORTED, "rg_conv_proj_x3: row stride must be a multiple of 4");
-  if (n_nodes <= 0) return RG_OK;
-  constexpr int lds = x3_bytes(C, PQW);
-  RG_ENSURE_LDS(proj_x3_kernel, lds);
+template <typename P>
+static int conv_proj(const rg_layer* pq, const rg_layer* we, const float* x, int ldx, int n_nodes,
+                     float* pq_out, void* stream) {
+  constexpr int lds = P::image_bytes(C, PQW);
+  auto proj = proj_x3_kernel<P>;
+  RG_ENSURE_LDS(proj, lds);
   const long tiles = (n_nodes + 31) / 32;
   long blocks = (tiles + 3) / 4;
   if (blocks > 256) blocks = 256;
-  proj_x3_kernel<<<blocks, PFT, lds, (hipStream_t)stream>>>(x, ldx, n_nodes,
-                                                           (const char*)pq->w_packed, pq_out);
+  proj<<<blocks, PFT, lds, (hipStream_t)stream>>>(x, ldx, n_nodes, (const char*)pq->w_packed,
+                                                  we ? (const char*)we->w_packed : nullptr, pq_out);
   RG_LAUNCH_CHECK();
   return RG_OK;
+}
+
+extern "C" int rg_conv_proj_x3_for(const rg_layer* pq, const rg_layer* we, const float* x, int ldx,
+                                   int n_nodes, float* pq_out, void* stream) {
+  RG_REQUIRE(pq && pq->in_dim == C && pq->out_dim == PQW && !pq->norm_mu && pq->act == RG_ACT_NONE,
+             RG_ERR_UNSUPPORTED, "rg_conv_proj_x3: expects the 64 -> 256 projection");
+  RG_REQUIRE(ldx % 4 == 0, RG_ERR_UNSUPPORTED, "rg_conv_proj_x3: row stride must be a multiple of 4");
+  const bool h2 = pq->flags & RG_LAYER_H2;
+  // an h2 projection writes its rows in the units of the W_e image that accumulates onto them
+  RG_REQUIRE(!h2 || (we && (we->flags & RG_LAYER_H2) && we->in_dim == C && we->out_dim == HID),
+             RG_ERR_ARG, "rg_conv_proj_x3: an RG_LAYER_H2 projection needs its layer's RG_LAYER_H2 W_e image");
+  RG_REQUIRE(h2 || !we || !(we->flags & RG_LAYER_H2), RG_ERR_ARG,
+             "rg_conv_proj_x3: the projection and the W_e image are packed under different schemes");
+  if (n_nodes <= 0) return RG_OK;
+  return h2 ? conv_proj<H2P>(pq, we, x, ldx, n_nodes, pq_out, stream)
+            : conv_proj<B3>(pq, we, x, ldx, n_nodes, pq_out, stream);
+}
+
+extern "C" int rg_conv_proj_x3(const rg_layer* pq, const float* x, int ldx, int n_nodes,
+                               float* pq_out, void* stream) {
+  return rg_conv_proj_x3_for(pq, nullptr, x, ldx, n_nodes, pq_out, stream);
 }
 
 extern "C" size_t rg_conv_x3_blocks_bytes(int n_nodes) {
@@ -1256,19 +1355,30 @@ extern "C" int rg_conv_x3_blocks(const int* seg_ptr, int n_nodes, int* table, vo
   return x3_wave_table(seg_ptr, n_nodes, table, stream);
 }
 
-static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, int aggr, const float* x,
+static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, const rg_layer* next_we,
+                         int aggr, const float* x,
                          int ldx, const float* e, int lde, const float* pq, const int* seg_ptr,
                          const int* src, const int* dst, int n_nodes, float* x_out, int ld_out,
                          float* pq_out, const int* table, void* workspace, size_t workspace_bytes,
                          void* stream);
+
+extern "C" int rg_conv_layer_x3_for(const rg_layer* layers, const rg_layer* next_pq,
+                                    const rg_layer* next_we, int aggr, const float* x, int ldx,
+                                    const float* e, int lde, const float* pq, const int* seg_ptr,
+                                    const int* src, const int* dst, int n_nodes, float* x_out,
+                                    int ld_out, float* pq_out, const int* table, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  return conv_layer_x3(layers, next_pq, next_we, aggr, x, ldx, e, lde, pq, seg_ptr, src, dst,
+                       n_nodes, x_out, ld_out, pq_out, table, workspace, workspace_bytes, stream);
+}
 
 extern "C" int rg_conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, int aggr,
                                 const float* x, int ldx, const float* e, int lde, const float* pq,
                                 const int* seg_ptr, const int* src, const int* dst, int n_nodes,
                                 float* x_out, int ld_out, float* pq_out, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-  return conv_layer_x3(layers, next_pq, aggr, x, ldx, e, lde, pq, seg_ptr, src, dst, n_nodes,
-                       x_out, ld_out, pq_out, nullptr, workspace, workspace_bytes, stream);
+  return conv_layer_x3(layers, next_pq, nullptr, aggr, x, ldx, e, lde, pq, seg_ptr, src, dst,
+                       n_nodes, x_out, ld_out, pq_out, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rg_conv_layer_x3_blocks(const rg_layer* layers, const rg_layer* next_pq, int aggr,
@@ -1278,12 +1388,51 @@ extern "C" int rg_conv_layer_x3_blocks(const rg_layer* layers, const rg_layer* n
                                        float* pq_out, const int* table, void* workspace,
                                        size_t workspace_bytes, void* stream) {
   RG_REQUIRE(table, RG_ERR_ARG, "rg_conv_layer_x3_blocks: table from rg_conv_x3_blocks");
-  return conv_layer_x3(layers, next_pq, aggr, x, ldx, e, lde, pq, seg_ptr, src, dst, n_nodes,
-                       x_out, ld_out, pq_out, table, workspace, workspace_bytes, stream);
+  return conv_layer_x3(layers, next_pq, nullptr, aggr, x, ldx, e, lde, pq, seg_ptr, src, dst,
+                       n_nodes, x_out, ld_out, pq_out, table, workspace, workspace_bytes, stream);
 }
 
-static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, int aggr,
-                         const float* x, int ldx, const float* e, int lde, const float* pq,
+// the two launches of one layer under scheme P
+template <typename P>
+static int conv_launch(const Args& a0, bool cent, int n_nodes, const int* seg_ptr, const int* table,
+                       void* workspace, void* stream) {
+  Args a = a0;
+  // (the one-wave launch addresses Q rows with 32-bit byte offsets: < 4 Mi nodes)
+  if (cent && n_nodes < (1 << 22)) {
+    const int* wtab = table;
+    if (!wtab) {  // no per-graph table: build the wave ranges into the workspace
+      int* ws_tab = (int*)((char*)workspace + CTR_BYTES + x3_agg_bytes(n_nodes));
+      const int rc = x3_wave_table(seg_ptr, n_nodes, ws_tab, stream);
+      if (rc != RG_OK) return rc;
+      wtab = ws_tab;
+    }
+    a.slabs = x3_slabs(n_nodes);
+    auto edge = conv_x3_sp_kernel<P, true>;
+    RG_ENSURE_LDS(edge, sp::Lay<P>::LDS);
+    edge<<<x3_sp_groups(n_nodes), sp::FT, sp::Lay<P>::LDS, (hipStream_t)stream>>>(a, wtab);
+    RG_LAUNCH_CHECK();
+  } else {  // (a wave table, if given, is not used: NBLK-node blocks)
+    int blocks = 256;  // one workgroup per CU (LDS); a multiple of the 8 XCDs
+    const int need = (a.n_blocks + NW - 1) / NW;
+    if (blocks > need) blocks = (need + NXCD - 1) / NXCD * NXCD;
+    if (blocks < NXCD) blocks = NXCD;
+    a.steal = a.n_blocks >= 2 * blocks * NW;
+    auto edge = cent ? conv_x3_kernel<P, true> : conv_x3_kernel<P, false>;
+    RG_ENSURE_LDS(edge, Blk<P>::LDS_BYTES);
+    edge<<<blocks, FT, Blk<P>::LDS_BYTES, (hipStream_t)stream>>>(a);
+    RG_LAUNCH_CHECK_ZERO(a.counters, CTR_BYTES, stream);
+  }
+  auto node = cent ? node_x3_kernel<P, true> : node_x3_kernel<P, false>;
+  RG_ENSURE_LDS(node, Node<P>::LDS);
+  const int tiles = (n_nodes + 31) / 32;
+  const int nblk = (tiles + NW_NODE - 1) / NW_NODE < 256 ? (tiles + NW_NODE - 1) / NW_NODE : 256;
+  node<<<nblk, NFT, Node<P>::LDS, (hipStream_t)stream>>>(a);
+  RG_LAUNCH_CHECK();
+  return RG_OK;
+}
+
+static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, const rg_layer* next_we,
+                         int aggr, const float* x, int ldx, const float* e, int lde, const float* pq,
                          const int* seg_ptr, const int* src, const int* dst, int n_nodes,
                          float* x_out, int ld_out, float* pq_out, const int* table,
                          void* workspace, size_t workspace_bytes, void* stream) {
@@ -1304,6 +1453,17 @@ static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, int ag
   RG_REQUIRE(!next_pq || (next_pq->in_dim == C && next_pq->out_dim == PQW && !next_pq->norm_mu &&
                           next_pq->act == RG_ACT_NONE),
              RG_ERR_UNSUPPORTED, "rg_conv_layer_x3: next_pq must be the 64 -> 256 projection");
+  // one term scheme over the layer's images, next_pq and next_we included; an h2 next_pq
+  // writes its rows in the units of the next layer's W_e image (next_we)
+  const int h2 = m0.flags & RG_LAYER_H2;
+  RG_REQUIRE((m1.flags & RG_LAYER_H2) == h2 && (u.flags & RG_LAYER_H2) == h2 &&
+                 (!next_pq || (next_pq->flags & RG_LAYER_H2) == h2) &&
+                 (!next_we || (next_we->flags & RG_LAYER_H2) == h2),
+             RG_ERR_ARG, "rg_conv_layer_x3: RG_LAYER_H2 on every image of a layer or on none");
+  RG_REQUIRE(!next_we || (next_pq && next_we->in_dim == C && next_we->out_dim == HID), RG_ERR_ARG,
+             "rg_conv_layer_x3: next_we is the next layer's W_e image and goes with next_pq");
+  RG_REQUIRE(!h2 || !next_pq || next_we, RG_ERR_ARG,
+             "rg_conv_layer_x3: an RG_LAYER_H2 next_pq needs next_we (rg_conv_layer_x3_for)");
   RG_REQUIRE(ldx % 4 == 0 && ld_out % 4 == 0 && lde % 4 == 0, RG_ERR_UNSUPPORTED,
              "rg_conv_layer_x3: row strides must be multiples of 4");
   RG_REQUIRE(x != x_out, RG_ERR_ARG, "rg_conv_layer_x3: x_out must not alias x");
@@ -1327,6 +1487,7 @@ static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, int ag
   a.w[1] = (const char*)m1.w_packed;
   a.w[2] = (const char*)u.w_packed;
   a.wpq = next_pq ? (const char*)next_pq->w_packed : nullptr;
+  a.we_next = next_we ? (const char*)next_we->w_packed : nullptr;
   const rg_layer* ls[3] = {&m0, &m1, &u};
   for (int l = 0; l < 3; ++l) {
     a.mu[l] = ls[l]->norm_mu;
@@ -1338,36 +1499,6 @@ static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, int ag
   a.n_nodes = n_nodes;
   a.n_blocks = (n_nodes + NBLK - 1) / NBLK;
   a.aggr_mean = aggr == RG_REDUCE_MEAN;
-  // (the one-wave launch addresses Q rows with 32-bit byte offsets: < 4 Mi nodes)
-  if (cent && n_nodes < (1 << 22)) {
-    const int* wtab = table;
-    if (!wtab) {  // no per-graph table: build the wave ranges into the workspace
-      int* ws_tab = (int*)((char*)workspace + CTR_BYTES + x3_agg_bytes(n_nodes));
-      const int rc = x3_wave_table(seg_ptr, n_nodes, ws_tab, stream);
-      if (rc != RG_OK) return rc;
-      wtab = ws_tab;
-    }
-    a.slabs = x3_slabs(n_nodes);
-    auto edge = conv_x3_sp_kernel<true>;
-    RG_ENSURE_LDS(edge, sp::LDS);
-    edge<<<x3_sp_groups(n_nodes), sp::FT, sp::LDS, (hipStream_t)stream>>>(a, wtab);
-    RG_LAUNCH_CHECK();
-  } else {  // (a wave table, if given, is not used: NBLK-node blocks)
-  int blocks = 256;  // one workgroup per CU (LDS); a multiple of the 8 XCDs
-  const int need = (a.n_blocks + NW - 1) / NW;
-  if (blocks > need) blocks = (need + NXCD - 1) / NXCD * NXCD;
-  if (blocks < NXCD) blocks = NXCD;
-  a.steal = a.n_blocks >= 2 * blocks * NW;
-  auto edge = cent ? conv_x3_kernel<true> : conv_x3_kernel<false>;
-  RG_ENSURE_LDS(edge, LDS_BYTES);
-  edge<<<blocks, FT, LDS_BYTES, (hipStream_t)stream>>>(a);
-  RG_LAUNCH_CHECK_ZERO(a.counters, CTR_BYTES, stream);
-  }
-  auto node = cent ? node_x3_kernel<true> : node_x3_kernel<false>;
-  RG_ENSURE_LDS(node, NODE_LDS);
-  const int tiles = (n_nodes + 31) / 32;
-  const int nblk = (tiles + NW_NODE - 1) / NW_NODE < 256 ? (tiles + NW_NODE - 1) / NW_NODE : 256;
-  node<<<nblk, NFT, NODE_LDS, (hipStream_t)stream>>>(a);
-  RG_LAUNCH_CHECK();
-  return RG_OK;
+  return h2 ? conv_launch<H2P>(a, cent != 0, n_nodes, seg_ptr, table, workspace, stream)
+            : conv_launch<B3>(a, cent != 0, n_nodes, seg_ptr, table, workspace, stream);
 }

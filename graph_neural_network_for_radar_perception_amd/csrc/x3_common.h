@@ -2,7 +2,7 @@
 // two TERM SCHEMES (a compile-time policy: plane count, element type, split, MFMA, product
 // list), B3 and H2P below.
 //
-// b3 (B3) -- three bf16 terms, six products (the conv layer's kernels; the chains on request).
+// b3 (B3) -- three bf16 terms, six products (on request: engine.X3_TERMS = 'b3').
 // Every f32 operand is split EXACTLY into three bf16 terms, v = v0 + v1 + v2 (round to
 // nearest even at each step: v0 = bf16(v), v1 = bf16(v - v0), v2 = bf16(v - v0 - v1); the
 // residues are exact in f32, and the third term holds the last 8 significant bits), and a
@@ -14,7 +14,7 @@
 // Six 32-cycle bf16 MFMAs replace eight 64-cycle f32 MFMAs per 16-deep k-step: 2.7x the
 // matrix rate of v_mfma_f32_32x32x2_f32.
 //
-// h2 (H2P) -- two IEEE f16 terms, three products (the chains' default).
+// h2 (H2P) -- two IEEE f16 terms, three products (the default of the chains and the conv layer).
 // v = v0 + v1 + r with v0 = f16(v), v1 = f16(v - v0); v - v0 is exact in f32 and |r| <= 2^-21 |v| while v1 is a normal f16.
 // A product is a0 w1 + a1 w0 + a0 w0 (small terms first) on v_mfma_f32_32x32x16_f16 with f32
 // accumulation; the dropped a1 w1 and the two r terms are each <= 2^-21 |a w|, the size of

@@ -45,9 +45,10 @@ HALF = ('bf16', 'fp16')
 def _half_flag(dtype: str) -> int:
     return nat.RG_PACK_F16 if dtype == 'fp16' else 0
 
-# Arithmetic of the fused fp32 conv layer: 'x3' = float32 products from exact three-term
-# bf16 splits on the bf16 matrix cores (rg_conv_layer_x3, one launch per layer, the next
-# layer's projections fused into the update); 'mfma_f32' = v_mfma_f32_32x32x2_f32
+# Arithmetic of the fused fp32 conv layer: 'x3' = float32 products from 16-bit splits on the
+# 16-bit matrix cores under the term scheme X3_TERMS below (rg_conv_layer_x3_for, an edge and a
+# node launch per layer, the next layer's projections fused into the node launch);
+# 'mfma_f32' = v_mfma_f32_32x32x2_f32
 # (rg_conv_layer_f32).  Both keep float32 accuracy (tests/test_gpu_f32.py runs both by
 # setting this attribute; nothing reads the environment).
 F32_ARITH = 'x3'
@@ -55,8 +56,9 @@ F32_ARITH = 'x3'
 # IEEE fp16 splits, three MFMA products per f32 product (RG_PACK_H2: half the matrix work,
 # float32-class results, every converted value |a| < 2**15 -- an overflow comes back
 # non-finite); 'b3' = exact three-term bf16 splits, six products (RG_PACK_X3: no range
-# limit).  The fused conv layers run 'b3' either way.  Read when a chain is first packed or
-# called after a change.
+# limit).  The fused 'x3' conv layers (rg_conv_layer_x3_for) follow it too: under 'h2' the
+# domain also covers the aggregate the node launch reads (with 'add', degree times the
+# message bound).  Read when a chain or layer is first packed or called after a change.
 X3_TERMS = 'h2'
 H2_MAX_ABS = 2.0 ** 15   # the 'h2' domain: every value a chain converts to fp16 is below this
 
@@ -915,6 +917,7 @@ class ConvPlan:
                            torch.cat((b, torch.zeros_like(b)), 0).contiguous(), None, None, 'none')
             we = LayerSpec(W[:, 2 * C:].contiguous(), None, m0.mu, m0.std, m0.act)
             return [pq, we, m1, u], (nat.RG_PACK_F32_FAST,) * 4
+        # (X3: the term-scheme flag, replaced per engine.X3_TERMS by fused_fmts)
         X3, CEN = nat.RG_PACK_X3, nat.RG_PACK_CENTERED
         # normalised layers packed zero-mean over their outputs (the kernel then skips
         # the mean pass): msg0 is centred here as a whole -- its x_i, x_j and edge
@@ -956,7 +959,7 @@ class ConvPlan:
         derived = self._fused_specs()
         if derived is None:
             return
-        specs, self.fused_fmts = derived
+        specs, self._fused_fmts = derived
         if self.images is None:
             self.images = PackedImages(specs, self.device, self.msg.specs + self.upd.specs)
         self.images.specs = specs
@@ -967,6 +970,18 @@ class ConvPlan:
         self._ws = {}
         self.x3_pq = None   # fp32 x3: projections of a standalone run_fused call
         self.fused = True
+
+    @property
+    def fused_fmts(self) -> tuple:
+        """Formats of the fused set; the fp32 'x3' layer's under the current engine.X3_TERMS
+        (the five images all RG_PACK_H2 or all RG_PACK_X3, centred alike)."""
+        if self.f32_arith != 'x3':
+            return self._fused_fmts
+        if X3_TERMS == 'b3':
+            return self._fused_fmts
+        if X3_TERMS == 'h2':
+            return tuple((f & ~nat.RG_PACK_X3) | nat.RG_PACK_H2 for f in self._fused_fmts)
+        raise ValueError(f"engine.X3_TERMS must be 'h2' or 'b3', not {X3_TERMS!r}")
 
     def _layers(self, first: int = 0):
         """The fused set's descriptors from layer `first` on."""
@@ -1007,10 +1022,12 @@ class ConvPlan:
                 and x.dtype == torch.float32 and e.dtype == torch.float32)
 
     def project_x3(self, x, pq) -> bool:
-        """P | Q of the first x3 layer (rg_conv_proj_x3); False when the kernel does not
-        take this layer (the caller then runs the layer unfused)."""
-        rc = nat.lib().rg_conv_proj_x3(self._layers(3), x.data_ptr(), x.stride(0), x.shape[0],
-                                       pq.data_ptr(), nat.stream_ptr(x.device))
+        """P | Q of the first x3 layer (rg_conv_proj_x3_for: in the units of this layer's W_e
+        image under 'h2'); False when the kernel does not take this layer (the caller then
+        runs the layer unfused)."""
+        rc = nat.lib().rg_conv_proj_x3_for(self._layers(3), self._layers(), x.data_ptr(),
+                                           x.stride(0), x.shape[0], pq.data_ptr(),
+                                           nat.stream_ptr(x.device))
         if rc == nat.RG_ERR_UNSUPPORTED:
             self.fused_ok = False
             return False
@@ -1018,21 +1035,19 @@ class ConvPlan:
         return True
 
     def run_x3(self, x, e, g, x_out, pq, nxt=None, pq_out=None) -> bool:
-        """One rg_conv_layer_x3 launch; with nxt (the next ConvPlan, also x3) it also writes
-        the next layer's P | Q into pq_out."""
+        """One rg_conv_layer_x3_for call; with nxt (the next ConvPlan, also x3) it also writes
+        the next layer's P | Q into pq_out (under 'h2' in the units of nxt's W_e image)."""
         lib = nat.lib()
         st = nat.stream_ptr(x.device)
         ws = self.workspace(lib.rg_conv_layer_x3_workspace_size(g.n_nodes), st)
         tbl = g.conv_x3_blocks()
-        args = (self._layers(), nxt._layers(4) if nxt is not None else None,
-                nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0), e.data_ptr(), e.stride(0),
-                pq.data_ptr(), g.seg_ptr.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(), g.n_nodes,
-                x_out.data_ptr(), x_out.stride(0), nat.ptr(pq_out))
-        tail = (ws.data_ptr(), ws.numel(), st)
-        if tbl is not None:
-            rc = lib.rg_conv_layer_x3_blocks(*args, tbl.data_ptr(), *tail)
-        else:
-            rc = lib.rg_conv_layer_x3(*args, *tail)
+        rc = lib.rg_conv_layer_x3_for(
+            self._layers(), nxt._layers(4) if nxt is not None else None,
+            nxt._layers() if nxt is not None else None,
+            nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0), e.data_ptr(), e.stride(0),
+            pq.data_ptr(), g.seg_ptr.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(), g.n_nodes,
+            x_out.data_ptr(), x_out.stride(0), nat.ptr(pq_out),
+            tbl.data_ptr() if tbl is not None else None, ws.data_ptr(), ws.numel(), st)
         if rc == nat.RG_ERR_UNSUPPORTED:
             self.fused_ok = False
             return False

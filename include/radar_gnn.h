@@ -298,7 +298,7 @@ typedef struct rg_layer {
 #define RG_LAYER_F16 2      /* w_packed holds fp16 fragments (RG_PACK_F16): the fast chain /
                                fused conv then read and write RG_F16 activations */
 #define RG_LAYER_H2 4       /* w_packed was packed with RG_PACK_H2 (rg_mlp_chain_x3: every layer
-                               of a chain, or none) */
+                               of a chain, or none; rg_conv_layer_x3_for: every image, or none) */
 
 #define RG_MAX_LAYERS 8
 
@@ -414,7 +414,14 @@ int rg_conv_layer_f32(const rg_layer* layers, int aggr, const float* x, int ldx,
  *             [b_msg0'; 0]): then pq_out [n_nodes][256] receives it from x_out's registers
  *   workspace rg_conv_layer_x3_workspace_size(n_nodes) bytes, block counters ZEROED before
  *             the first call (every completed launch leaves them zero); one per stream.
- * Same results contract as rg_conv_layer_f32 (sum in edge order, mean = sum / max(deg, 1)). */
+ * Same results contract as rg_conv_layer_f32 (sum in edge order, mean = sum / max(deg, 1)).
+ * With RG_PACK_H2 in place of RG_PACK_X3 on EVERY image (RG_LAYER_H2 on layers[0..2], next_pq
+ * and next_we; a mixture is RG_ERR_ARG) the products are two-term fp16 splits, three MFMAs
+ * instead of six, as in rg_mlp_chain_x3: float32-class results, every converted value -- x,
+ * e, the normalised hidden rows and the AGGREGATE -- limited to |a| < 2^15 (beyond it rows
+ * come back non-finite).  Each h2 image carries its own power-of-two scale, and pq rows are
+ * then held in the units of the W_e image that accumulates onto them: their writer needs
+ * that image (rg_conv_proj_x3_for's we, rg_conv_layer_x3_for's next_we). */
 size_t rg_conv_layer_x3_workspace_size(int n_nodes);
 int rg_conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, int aggr, const float* x,
                      int ldx, const float* e, int lde, const float* pq, const int* seg_ptr,
@@ -440,6 +447,19 @@ int rg_conv_x3_blocks(const int* seg_ptr, int n_nodes, int* table, void* stream)
  * RG_PACK_FAST_IN | RG_PACK_X3 (64 -> 256, bias [b_msg0; 0]). */
 int rg_conv_proj_x3(const rg_layer* pq, const float* x, int ldx, int n_nodes, float* pq_out,
                     void* stream);
+/* The same for either term scheme: we = layers[0] (the W_e image) of the layer that will read
+ * pq_out -- required when pq is RG_LAYER_H2 (then also RG_LAYER_H2), ignored (may be NULL)
+ * under RG_PACK_X3.  rg_conv_proj_x3 is this call with we = NULL. */
+int rg_conv_proj_x3_for(const rg_layer* pq, const rg_layer* we, const float* x, int ldx,
+                        int n_nodes, float* pq_out, void* stream);
+/* rg_conv_layer_x3 (table NULL) / rg_conv_layer_x3_blocks for either term scheme: next_we =
+ * layers[0] of the NEXT layer, the consumer of pq_out -- required with an RG_LAYER_H2
+ * next_pq, NULL without next_pq. */
+int rg_conv_layer_x3_for(const rg_layer* layers, const rg_layer* next_pq, const rg_layer* next_we,
+                         int aggr, const float* x, int ldx, const float* e, int lde,
+                         const float* pq, const int* seg_ptr, const int* src, const int* dst,
+                         int n_nodes, float* x_out, int ld_out, float* pq_out, const int* table,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* One fused residual_graph_conv_block (gnn_blocks.py:96-113) for the shipped
  * widths (node / edge channels 64, msg MLP 192->128->64, update 128->64, all with
