@@ -164,6 +164,8 @@ _SIGNATURES = {
                                  _P, _I, _I, _P, _P, _P, _I, _P, _I, _P]),
     'rg_mlp_chain_x3': (_I, [ctypes.POINTER(rg_layer), _I, _L, _P, _I, _P, _I, _I, _P, _P, _P,
                              _I, _P]),
+    'rg_mlp_chain_x3_split': (_I, [ctypes.POINTER(rg_layer), _I, _L, _P, _I, _P, _I, _I, _P, _P,
+                                   _P, _I, _P]),
     'rg_h2_mfma_probe': (_I, [_P, _P, _P, _P]),
     'rg_conv_layer_f32_workspace_size': (_S, [_I]),
     'rg_conv_layer_f32': (_I, [ctypes.POINTER(rg_layer), _I, _P, _I, _P, _I, _P, _P, _P, _I, _P,
@@ -181,6 +183,9 @@ _SIGNATURES = {
     'rg_conv_layer_x3_for': (_I, [ctypes.POINTER(rg_layer), ctypes.POINTER(rg_layer),
                                   ctypes.POINTER(rg_layer), _I, _P, _I, _P, _I, _P, _P, _P, _P,
                                   _I, _P, _I, _P, _P, _P, _S, _P]),
+    'rg_conv_layer_x3_split_for': (_I, [ctypes.POINTER(rg_layer), ctypes.POINTER(rg_layer),
+                                        ctypes.POINTER(rg_layer), _I, _P, _I, _P, _I, _P, _P, _P,
+                                        _P, _I, _P, _I, _P, _P, _P, _S, _P]),
     'rg_conv_layer_workspace_size': (_S, []),
     'rg_conv_layer_fused': (_I, [ctypes.POINTER(rg_layer), ctypes.POINTER(rg_layer), _I, _P, _I,
                                  _P, _I, _P, _P, _P, _I, _P, _I, _P, _P]),

@@ -140,17 +140,49 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MT], const float* nrm) {
   }
 }
 
-template <int RT, int MT, bool FULL = false>
+// FULL: 0 the general stores, 1 the encoders' branch-free buffer stores, 2 the same as split
+// rows (pack_layout.h; h2 only): the row's h2 terms in the place of its float32 values
+template <int RT, int MT, int FULL = 0>
 __device__ __forceinline__ void store_rows(const f32x16 (&acc)[RT][MT], const Args& a, long row0,
                                            long rows, int lane) {
   const int r = lane & 31, h = lane >> 5;
   const int out = a.out_real;
-  if constexpr (FULL) {
+  if constexpr (FULL != 0) {
     // full-width, 16-B aligned rows (host-checked): branch-free buffer stores, a row past the
     // end dropped by the hardware (offset past the buffer) -- the compiler then counts these
     // stores, and the next tile's wait for its prefetched inputs does not wait for them too
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         a.out, 0, (int)(((rows - 1) * a.ld_out + 32 * MT) * 4), 0x00020000);
+    if constexpr (FULL == 2) {
+      // lane (r, h) holds features 32m + 8g + 4h + t: half h of group 4m + g.  One split of
+      // the eight values of groups g, g + 1 (the conv's own split8_h2: the same bits), then
+      // per group the lane pair exchanges halves -- v_permlane32_swap(heads, residues) leaves
+      // h = 0 with both halves of the heads and h = 1 with both halves of the residues: one
+      // 16-byte store per lane and group (two 8-byte stores per group measured 40 us slower)
+      static_assert(32 * MT == SPLIT_ROW_W, "split rows are 64 wide");
+      typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        const long row = row0 + 32 * t + r;
+        const int off = row < rows ? (int)(row * a.ld_out * 4) : 0x7ffff000;
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+          for (int gp = 0; gp < 2; ++gp) {
+            const H2 sp = split_acc_of<H2P>(acc[t][m], gp);
+            const u32x4 w0 = __builtin_bit_cast(u32x4, sp.p0), w1 = __builtin_bit_cast(u32x4, sp.p1);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              const int gb = SPLIT_ROW_BYTES / 8 * (4 * m + 2 * gp + u);  // the group's 32 bytes
+              const auto s0 = __builtin_amdgcn_permlane32_swap(w0[2 * u], w1[2 * u], false, false);
+              const auto s1 = __builtin_amdgcn_permlane32_swap(w0[2 * u + 1], w1[2 * u + 1], false, false);
+              __builtin_amdgcn_raw_buffer_store_b128((u32x4_t){s0[0], s1[0], s0[1], s1[1]}, rs,
+                                                     off + 16 * h + gb, 0, 0);
+            }
+          }
+      }
+      return;
+    }
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
       const long row = row0 + 32 * t + r;
@@ -296,7 +328,7 @@ __device__ __forceinline__ void add_bias(f32x16 (&acc)[RT][MT], const float* bia
 // pre: run after the last layer's MFMAs are issued, before its epilogue (the encoders' next-tile
 // input loads: the only loads then in flight, so no weight wait stalls behind them)
 template <typename P, typename S, int SPEC, int LM, int l, int RT, int PMT, int PEND,
-          bool FULL = false, typename Pre = NoHook>
+          int FULL = 0, typename Pre = NoHook>
 __device__ __forceinline__ void run_rest(const Args& a, f32x16 (&prev)[RT][PMT], Pend (&pend)[RT],
                                          const char* lds, const float* nrm, long row0, long rows,
                                          int lane, Pre&& pre = Pre{}) {
@@ -403,7 +435,7 @@ __device__ __forceinline__ void run_pre(const Args& a, const char* lds, const fl
 
 // encoders: layer 0 (one k-step of <= 8 inputs, no normalisation) fused tile by tile into
 // layer 1: tile m0 of layer 0 is layer 1's k-steps 2 m0 and 2 m0 + 1
-template <typename P, typename S, int SPEC, int LM, int RT, typename Pre = NoHook>
+template <typename P, typename S, int SPEC, int LM, int RT, int SPLIT = 0, typename Pre = NoHook>
 __device__ __forceinline__ void run_fused01(const Args& a, const typename P::terms (&b0)[RT][1],
                                             const char* lds,
                                             const float* nrm, long row0, long rows, int lane,
@@ -458,21 +490,26 @@ __device__ __forceinline__ void run_fused01(const Args& a, const typename P::ter
     // with tile 1's last MFMAs)
     if (m0 + 1 < MT0) __builtin_amdgcn_sched_barrier(0);
   }
+  // (split rows go out by the buffer stores only)
+  static_assert(!SPLIT || RG_X3_ENC_BUF, "split rows need the encoders' buffer stores");
+  constexpr int FULL = SPLIT ? 2 : RG_X3_ENC_BUF;
   if constexpr (S::NL > 2) {
     Pend pn[RT];
     epilogue_next<P, SPEC, 1, MT1, RT>(acc, nrm, pn);
-    run_rest<P, S, SPEC, LM, 2, RT, MT1, pend_kind<SPEC, 1>(), RG_X3_ENC_BUF>(a, acc, pn, lds, nrm,
-                                                                            row0, rows, lane, pre);
+    run_rest<P, S, SPEC, LM, 2, RT, MT1, pend_kind<SPEC, 1>(), FULL>(a, acc, pn, lds, nrm, row0,
+                                                                     rows, lane, pre);
   } else {
     pre();
 #pragma unroll
     for (int t = 0; t < RT; ++t) epilogue<P, SPEC, 1, MT1>(acc[t], nrm);
-    store_rows<RT, MT1, RG_X3_ENC_BUF>(acc, a, row0, rows, lane);
+    store_rows<RT, MT1, FULL>(acc, a, row0, rows, lane);
   }
 }
 
-template <typename P, int MODE, int SPEC, int LM, int RT, int FT, int K0, int... Ns>
+// SPLIT (the encoders, h2): the output rows stored as split rows (store_rows FULL = 2)
+template <typename P, int MODE, int SPEC, int LM, int RT, int FT, int SPLIT, int K0, int... Ns>
 __global__ __launch_bounds__(FT) void chain_x3_kernel(Args a) {
+  static_assert(!SPLIT || (MODE == IN_SMALL && RG_X3_INPF && P::NP == 2), "split rows: h2 encoders");
   using S = Shape<P, K0, Ns...>;
   typedef typename P::terms T;
   constexpr int NL = S::NL;
@@ -584,7 +621,7 @@ __global__ __launch_bounds__(FT) void chain_x3_kernel(Args a) {
       }
     }
     if constexpr (MODE == IN_SMALL && RG_X3_INPF)
-      run_fused01<P, S, SPEC, LM, RT>(a, b0, lds, nrm, row0, rows, lane, [&]() {
+      run_fused01<P, S, SPEC, LM, RT, SPLIT>(a, b0, lds, nrm, row0, rows, lane, [&]() {
         if (tile + tstride < ntiles) load_in(tile + tstride);
       });
     else if constexpr (MODE == IN_SMALL)
@@ -595,12 +632,12 @@ __global__ __launch_bounds__(FT) void chain_x3_kernel(Args a) {
   }
 }
 
-template <typename P, int MODE, int SPEC, int LM, int RT, int FT, int K0, int... Ns>
+template <typename P, int MODE, int SPEC, int LM, int RT, int FT, int SPLIT, int K0, int... Ns>
 static int launch(const Args& a, hipStream_t st) {
   using S = Shape<P, K0, Ns...>;
   constexpr int lds = S::lds_bytes(LM);
   static_assert(lds <= DYN_LDS_MAX, "chain_x3: LDS image too large");
-  auto kern = chain_x3_kernel<P, MODE, SPEC, LM, RT, FT, K0, Ns...>;
+  auto kern = chain_x3_kernel<P, MODE, SPEC, LM, RT, FT, SPLIT, K0, Ns...>;
   RG_ENSURE_LDS(kern, lds);
   const long tiles = (a.rows + 32 * RT - 1) / (32 * RT);
   long blocks = (tiles + FT / 64 - 1) / (FT / 64);
@@ -614,6 +651,7 @@ static int launch(const Args& a, hipStream_t st) {
 
 struct Key {
   int mode, k0, sp, nl;
+  int split;  // the output as split rows (rg_mlp_chain_x3_split)
   int n[RG_MAX_LAYERS];
 };
 
@@ -647,7 +685,14 @@ static bool match(const Key& k, int mode, int k0, int sp, std::initializer_list<
 template <typename P>
 static int dispatch(const Key& k, const Args& a, hipStream_t st) {
 #define RG_X3C(MODE, K0, SP, LM, RT, FT, ...) \
-  if (match(k, MODE, K0, SP, {__VA_ARGS__})) return launch<P, MODE, SP, LM, RT, FT, K0, __VA_ARGS__>(a, st);
+  if (!k.split && match(k, MODE, K0, SP, {__VA_ARGS__}))    \
+    return launch<P, MODE, SP, LM, RT, FT, 0, K0, __VA_ARGS__>(a, st);
+  // the same shape writing split rows (h2 only)
+#define RG_X3CS(MODE, K0, SP, LM, RT, FT, ...)                          \
+  if constexpr (P::NP == 2) {                                           \
+    if (k.split && match(k, MODE, K0, SP, {__VA_ARGS__}))               \
+      return launch<P, MODE, SP, LM, RT, FT, 1, K0, __VA_ARGS__>(a, st); \
+  }
   constexpr int ALL = P::NP == 3 ? 07777777 : 03333333;  // every plane of every layer in LDS
   // the encoders' LDS residency: b3 layer 0 + planes 0, 1 of layer 1 (153 KiB of the edge
   // encoder's 361 KiB); h2 layer 0 + both planes of layer 1 (144 KiB of 241 KiB: the next
@@ -660,6 +705,8 @@ static int dispatch(const Key& k, const Args& a, hipStream_t st) {
   RG_X3C(MODE, K0, spec(NM, AM, true), LM, RT, FT, __VA_ARGS__)         \
   RG_X3C(MODE, K0, spec(NM, AM, false), LM, RT, FT, __VA_ARGS__)
   RG_X3C2(IN_SMALL, 7, 0b1110, 0b1111, ENC, RG_X3_ENC_RT, EFT, 256, 128, 128, 64)
+  RG_X3CS(IN_SMALL, 7, spec(0b1110, 0b1111, true), ENC, RG_X3_ENC_RT, EFT, 256, 128, 128, 64)
+  RG_X3CS(IN_SMALL, 7, spec(0b1110, 0b1111, false), ENC, RG_X3_ENC_RT, EFT, 256, 128, 128, 64)
   // node encoder 6 -> 256 -> 128 -> 64
   RG_X3C2(IN_SMALL, 6, 0b110, 0b111, ENC, RG_X3_ENC_RT, EFT, 256, 128, 64)
   // task heads: 3-block stem + FFN_TaskSpecificHead (ffn + bare Linear -> 7 / 2, padded)
@@ -678,6 +725,7 @@ static int dispatch(const Key& k, const Args& a, hipStream_t st) {
   RG_X3C2(IN_DENSE, 64, 0b111, 0b111, ALL, 1, 512, 64, 64, 64)  // (176 B of spills at 768)
   RG_X3C2(IN_DENSE, 64, 0b01, 0b01, ALL, 1, RG_X3_HEAD_FT, 64, 32)
 #undef RG_X3C2
+#undef RG_X3CS
 #undef RG_X3C
   return RG_ERR_UNSUPPORTED;
 }
@@ -714,19 +762,36 @@ extern "C" int rg_h2_mfma_probe(const uint16_t* a, const uint16_t* b, float* c, 
 
 static int chain_x3(const rg_layer* layers, int n_layers, long rows, const int* rows_dev,
                     int in_mode, const float* in0, int ld0, int w0, const int* idx0,
-                    const int* idx1, float* out, int ld_out, void* stream);
+                    const int* idx1, float* out, int ld_out, bool split, void* stream);
 
 extern "C" int rg_mlp_chain_x3(const rg_layer* layers, int n_layers, long rows, const int* rows_dev,
                                int in_mode, const float* in0, int ld0, int w0, const int* idx0,
                                const int* idx1, float* out, int ld_out, void* stream) {
   return chain_x3(layers, n_layers, rows, rows_dev, in_mode, in0, ld0, w0, idx0, idx1, out,
-                  ld_out, stream);
+                  ld_out, false, stream);
+}
+
+extern "C" int rg_mlp_chain_x3_split(const rg_layer* layers, int n_layers, long rows,
+                                     const int* rows_dev, int in_mode, const float* in0, int ld0,
+                                     int w0, const int* idx0, const int* idx1, void* out,
+                                     int ld_out, void* stream) {
+  return chain_x3(layers, n_layers, rows, rows_dev, in_mode, in0, ld0, w0, idx0, idx1,
+                  (float*)out, ld_out, true, stream);
 }
 
 static int chain_x3(const rg_layer* layers, int n_layers, long rows, const int* rows_dev,
                     int in_mode, const float* in0, int ld0, int w0, const int* idx0,
-                    const int* idx1, float* out, int ld_out, void* stream) {
+                    const int* idx1, float* out, int ld_out, bool split, void* stream) {
   RG_REQUIRE(n_layers >= 1 && n_layers <= RG_MAX_LAYERS, RG_ERR_ARG, "rg_mlp_chain_x3: n_layers");
+  if (split) {  // split rows: an h2 chain's full-width rows of 64, 16-B aligned, back to back
+    bool h2all = true;
+    for (int l = 0; l < n_layers; ++l) h2all = h2all && (layers[l].flags & RG_LAYER_H2);
+    RG_REQUIRE(h2all, RG_ERR_ARG, "rg_mlp_chain_x3_split: RG_LAYER_H2 chains only");
+    RG_REQUIRE(layers[n_layers - 1].out_dim == SPLIT_ROW_W && ld_out == SPLIT_ROW_W, RG_ERR_ARG,
+               "rg_mlp_chain_x3_split: output rows of 64 values at a stride of 64");
+    RG_REQUIRE(out && (uintptr_t)out % 16 == 0, RG_ERR_ARG,
+               "rg_mlp_chain_x3_split: the output must be 16-byte aligned");
+  }
   RG_REQUIRE((in_mode != RG_IN_PAIRADD && in_mode != RG_IN_PAIRPRE) || (idx0 && idx1), RG_ERR_ARG,
              "rg_mlp_chain_x3: RG_IN_PAIRADD / RG_IN_PAIRPRE need idx0 and idx1");
   RG_REQUIRE(in_mode != RG_IN_PAIRPRE || (w0 == layers[0].out_dim && ld0 % 4 == 0), RG_ERR_ARG,
@@ -749,6 +814,7 @@ static int chain_x3(const rg_layer* layers, int n_layers, long rows, const int* 
              "rg_mlp_chain_x3: dense input width / stride must be multiples of 16 / 4");
   k.k0 = w0;
   k.nl = n_layers;
+  k.split = split;
   int nm = 0, am = 0;
   for (int l = 0; l < n_layers; ++l) {
     const rg_layer& s = layers[l];

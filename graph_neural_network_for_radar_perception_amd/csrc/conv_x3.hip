@@ -761,10 +761,14 @@ __device__ __forceinline__ void sub_prod(f32x16 (&acc)[MT], const typename P::ve
   }
 }
 
-template <typename P, bool CENT>
+// ES (h2 only): a.e holds SPLIT ROWS (pack_layout.h) -- the edge encoder has already split the
+// rows, which are the same for every layer of a forward -- and the two 16-byte pieces a lane
+// loads per k-step ARE layer 1's B operand (heads, residues): no conversion in the tile loop
+template <typename P, bool CENT, bool ES = false>
 __global__ __launch_bounds__(sp::FT) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
   static_assert(CENT, "the one-wave edge launch takes centred layers");
+  static_assert(!ES || P::NP == 2, "split e rows are h2 terms");
   typedef sp::Lay<P> L;
   typedef typename P::terms Terms;
   typedef typename P::vec Vec;
@@ -838,6 +842,12 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
       ev[2 * i] = *(const f32x4*)(g + 16 * i);
       ev[2 * i + 1] = *(const f32x4*)(g + 16 * i + 4);
     }
+  };
+  // layer 1's B operand of one k-step from its two loaded pieces: split here, or (ES) the
+  // pieces themselves
+  auto e_terms = [&](const f32x4& lo, const f32x4& hi) {
+    if constexpr (ES) return Terms{__builtin_bit_cast(Vec, lo), __builtin_bit_cast(Vec, hi)};
+    else return P::split(lo, hi);
   };
   // P rows through a ring of the wave's last RING destinations in LDS (slot = node & 7): a
   // tile's P[dst] is one row per DESTINATION (~4 per kNN tile), gathered per edge it was 16
@@ -987,7 +997,7 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
   init_tile(d0, qn, acc1[0], 0);
   f32x4 pr[4];  // the ring rows of the next M-tile to initialise, read one sub-chunk ahead
   ring_p(d0, 1, pr);
-  Terms b1 = P::split(en[0], en[1]);
+  Terms b1 = e_terms(en[0], en[1]);
   uint32_t mask_c = tile_mask(0, d0, a.n_nodes);
   int d_c = d0;
   // the previous tile's state (none yet: no mask bits, zero messages)
@@ -1022,7 +1032,7 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
     //          the split of k-step 1; norm 2's statistics of tile t - 1
     wait_frags(A1[0]);
     lda1<P, 1>(aw, A1[1]);
-    Terms b1n = P::split(ev[2], ev[3]);
+    Terms b1n = e_terms(ev[2], ev[3]);
     init_from(pr, qn, acc1[1], 1);
     ring_p(d_c, 2, pr);
     x3_tile<P, 0>(acc1, A1[0], b1);
@@ -1050,7 +1060,7 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
     //          wave's LDS operations complete in order: no wait between them)
     wait_frags(A1[1]);
     lda1<P, 2>(aw, A1[0]);
-    b1 = P::split(ev[4], ev[5]);
+    b1 = e_terms(ev[4], ev[5]);
     norm2_apply(acc2p[0], pn2, 0, 4);
     sub_prod<P, 0, 5, 8>(acc1, A1[1], b1n);
     norm2_apply(acc2p[0], pn2, 4, 12);
@@ -1071,7 +1081,7 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
     //          sums; tile t + 1's e rows
     wait_frags(A1[0]);
     lda1<P, 3>(aw, A1[1]);
-    b1n = P::split(ev[6], ev[7]);
+    b1n = e_terms(ev[6], ev[7]);
     uint32_t kb[32];
     keeps(0, 16, mask_p, kb);
     sub_prod<P, 0, 3, 5>(acc1, A1[0], b1);
@@ -1197,7 +1207,7 @@ void conv_x3_sp_kernel(Args a, const int* __restrict__ wtab) {
     x3_prod<P, 0>(acc2, A2[1], b2n);
     lda1<P, 0>(aw, A1[0]);  // the next tile's first layer-1 fragments
     fence();
-    b1 = P::split(en[0], en[1]);
+    b1 = e_terms(en[0], en[1]);
     rest2(A2[1], b2n);
     ring_p(d_nn, 1, pr);
     const uint32_t mask_n = tile_mask(t + 1, d_nn, dl_c);
@@ -1360,7 +1370,7 @@ static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, const 
                          int ldx, const float* e, int lde, const float* pq, const int* seg_ptr,
                          const int* src, const int* dst, int n_nodes, float* x_out, int ld_out,
                          float* pq_out, const int* table, void* workspace, size_t workspace_bytes,
-                         void* stream);
+                         void* stream, bool es = false);
 
 extern "C" int rg_conv_layer_x3_for(const rg_layer* layers, const rg_layer* next_pq,
                                     const rg_layer* next_we, int aggr, const float* x, int ldx,
@@ -1370,6 +1380,18 @@ extern "C" int rg_conv_layer_x3_for(const rg_layer* layers, const rg_layer* next
                                     size_t workspace_bytes, void* stream) {
   return conv_layer_x3(layers, next_pq, next_we, aggr, x, ldx, e, lde, pq, seg_ptr, src, dst,
                        n_nodes, x_out, ld_out, pq_out, table, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rg_conv_layer_x3_split_for(const rg_layer* layers, const rg_layer* next_pq,
+                                          const rg_layer* next_we, int aggr, const float* x,
+                                          int ldx, const void* e_split, int lde, const float* pq,
+                                          const int* seg_ptr, const int* src, const int* dst,
+                                          int n_nodes, float* x_out, int ld_out, float* pq_out,
+                                          const int* table, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  return conv_layer_x3(layers, next_pq, next_we, aggr, x, ldx, (const float*)e_split, lde, pq,
+                       seg_ptr, src, dst, n_nodes, x_out, ld_out, pq_out, table, workspace,
+                       workspace_bytes, stream, true);
 }
 
 extern "C" int rg_conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, int aggr,
@@ -1393,12 +1415,15 @@ extern "C" int rg_conv_layer_x3_blocks(const rg_layer* layers, const rg_layer* n
 }
 
 // the two launches of one layer under scheme P
+// (the one-wave launch addresses Q rows with 32-bit byte offsets: < 4 Mi nodes)
+static bool x3_one_wave(bool cent, int n_nodes) { return cent && n_nodes < (1 << 22); }
+
+// es: a0.e holds split rows (h2, the one-wave launch: both checked by the caller)
 template <typename P>
-static int conv_launch(const Args& a0, bool cent, int n_nodes, const int* seg_ptr, const int* table,
-                       void* workspace, void* stream) {
+static int conv_launch(const Args& a0, bool cent, bool es, int n_nodes, const int* seg_ptr,
+                       const int* table, void* workspace, void* stream) {
   Args a = a0;
-  // (the one-wave launch addresses Q rows with 32-bit byte offsets: < 4 Mi nodes)
-  if (cent && n_nodes < (1 << 22)) {
+  if (x3_one_wave(cent, n_nodes)) {
     const int* wtab = table;
     if (!wtab) {  // no per-graph table: build the wave ranges into the workspace
       int* ws_tab = (int*)((char*)workspace + CTR_BYTES + x3_agg_bytes(n_nodes));
@@ -1408,6 +1433,9 @@ static int conv_launch(const Args& a0, bool cent, int n_nodes, const int* seg_pt
     }
     a.slabs = x3_slabs(n_nodes);
     auto edge = conv_x3_sp_kernel<P, true>;
+    if constexpr (P::NP == 2) {
+      if (es) edge = conv_x3_sp_kernel<P, true, true>;
+    }
     RG_ENSURE_LDS(edge, sp::Lay<P>::LDS);
     edge<<<x3_sp_groups(n_nodes), sp::FT, sp::Lay<P>::LDS, (hipStream_t)stream>>>(a, wtab);
     RG_LAUNCH_CHECK();
@@ -1435,7 +1463,7 @@ static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, const 
                          int aggr, const float* x, int ldx, const float* e, int lde, const float* pq,
                          const int* seg_ptr, const int* src, const int* dst, int n_nodes,
                          float* x_out, int ld_out, float* pq_out, const int* table,
-                         void* workspace, size_t workspace_bytes, void* stream) {
+                         void* workspace, size_t workspace_bytes, void* stream, bool es) {
   const rg_layer& m0 = layers[0];
   const rg_layer& m1 = layers[1];
   const rg_layer& u = layers[2];
@@ -1470,6 +1498,15 @@ static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, const 
   RG_REQUIRE(!pq_out || pq_out != pq, RG_ERR_ARG, "rg_conv_layer_x3: pq_out must not alias pq");
   RG_REQUIRE(workspace_bytes >= rg_conv_layer_x3_workspace_size(n_nodes), RG_ERR_ARG,
              "rg_conv_layer_x3: workspace too small");
+  if (es) {
+    // split e rows (pack_layout.h): h2 terms in whole 256-byte rows, read 16 bytes at a time
+    RG_REQUIRE(h2, RG_ERR_ARG, "rg_conv_layer_x3_split_for: split e rows need RG_LAYER_H2 images");
+    RG_REQUIRE(lde == SPLIT_ROW_W, RG_ERR_ARG, "rg_conv_layer_x3_split_for: lde must be 64");
+    RG_REQUIRE(e && (uintptr_t)e % 16 == 0, RG_ERR_ARG,
+               "rg_conv_layer_x3_split_for: e must be 16-byte aligned");
+    // only the one-wave edge launch reads them (the block-queue launch takes float32 rows)
+    if (!x3_one_wave(cent != 0, n_nodes)) return RG_ERR_UNSUPPORTED;
+  }
   if (n_nodes <= 0) return RG_OK;
   Args a;
   memset(&a, 0, sizeof(a));
@@ -1499,6 +1536,6 @@ static int conv_layer_x3(const rg_layer* layers, const rg_layer* next_pq, const 
   a.n_nodes = n_nodes;
   a.n_blocks = (n_nodes + NBLK - 1) / NBLK;
   a.aggr_mean = aggr == RG_REDUCE_MEAN;
-  return h2 ? conv_launch<H2P>(a, cent != 0, n_nodes, seg_ptr, table, workspace, stream)
-            : conv_launch<B3>(a, cent != 0, n_nodes, seg_ptr, table, workspace, stream);
+  return h2 ? conv_launch<H2P>(a, cent != 0, es, n_nodes, seg_ptr, table, workspace, stream)
+            : conv_launch<B3>(a, cent != 0, false, n_nodes, seg_ptr, table, workspace, stream);
 }

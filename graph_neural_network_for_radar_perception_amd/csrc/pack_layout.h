@@ -147,4 +147,18 @@ RG_HD constexpr int bias_acc(int t) {
 }
 RG_HD constexpr int bias_of(int fmt, int t) { return is_wide(fmt) ? bias_acc(t) : bias_plain(t); }
 
+// ------------------------------------------------------------------ split rows
+// A SPLIT ROW holds the two h2 terms of a row of 64 float32 values v in the 256 bytes of the
+// float32 row itself (rg_mlp_chain_x3_split writes it, rg_conv_layer_x3_split_for reads it):
+// each aligned 32-byte group of eight values (features 8j .. 8j + 7) is the eight fp16 heads
+// a0 = fp16(v), 16 bytes, then the eight fp16 residues a1 = fp16(v - a0), 16 bytes.  Lane
+// (r, h) of the conv's edge launch reads the 16-byte pieces at float offsets 8h + 16i and
+// 8h + 16i + 4 of its row per k-step i -- group 2i + h: its heads and its residues, the MFMA B
+// operands of planes 0 and 1 as loaded.
+static constexpr int SPLIT_ROW_W = 64;                    // values per row
+static constexpr int SPLIT_ROW_BYTES = 4 * SPLIT_ROW_W;   // = the float32 row
+// byte offset in the row of the head / the residue of feature f
+RG_HD constexpr int split_row_head(int f) { return 32 * (f >> 3) + 2 * (f & 7); }
+RG_HD constexpr int split_row_res(int f) { return split_row_head(f) + 16; }
+
 }  // namespace rg

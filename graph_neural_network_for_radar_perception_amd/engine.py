@@ -75,6 +75,11 @@ def h2_scale_exp(max_abs: float) -> int:
     return min(max(13 - e, -64), 64)
 # fp32 link head with its first Linear per node (ModelPlans.link_pairs_pre); False = per pair
 LINK_PRE = True
+# 'h2' forward with every conv layer on the one-wave x3 edge launch: the edge encoder writes e
+# as split rows (rg_mlp_chain_x3_split: the two fp16 terms of each value in the float32's four
+# bytes) and the layers read them without splitting e again (rg_conv_layer_x3_split_for);
+# bit-identical outputs.  False = float32 e rows, split by every layer
+E_SPLIT = True
 # x3 conv over the per-graph work-block table (rg_conv_x3_blocks: LPT order, 8-node tail);
 # False = plain 32-node runs (same results)
 CONV_X3_TABLE = True
@@ -494,6 +499,29 @@ class ChainPlan:
                           'rg_frame_norm')
             cur = (dst, plan.out_dim, nat.IN_DENSE, None, 0, None, 0, None, None)
         return out
+
+    def run_split(self, rows: int, out: torch.Tensor, in0: torch.Tensor, w0: int,
+                  rows_dev=None) -> bool:
+        """The chain under 'h2' with its rows written into `out` (float32 [rows, 64], same
+        bytes) as split rows (rg_mlp_chain_x3_split); False, `out` untouched, when there is no
+        such kernel for this chain -- the caller then runs the chain as usual."""
+        if (self.pieces is not None or X3_TERMS != 'h2' or F32_ARITH != 'x3' or not self.use_fast
+                or self.dt != nat.RG_F32 or len(self.specs) > nat.MAX_LAYERS
+                or in0.dtype != torch.float32 or out.dtype != torch.float32
+                or self.out_dim != 64 or out.stride(0) != 64 or out.data_ptr() % 16
+                or self.x3_ok.get('split') is False):
+            return False
+        rc = nat.lib().rg_mlp_chain_x3_split(
+            self.images.get(self.x3_fmts())[0][0], len(self.specs), int(rows), nat.ptr(rows_dev),
+            nat.IN_DENSE, in0.data_ptr(), in0.stride(0), w0, None, None, out.data_ptr(),
+            out.stride(0), nat.stream_ptr(self.device))
+        if rc == nat.RG_ERR_UNSUPPORTED:
+            if _shape_refusal(rows, out, in0):
+                self.x3_ok['split'] = False
+            return False
+        nat.check(rc, 'rg_mlp_chain_x3_split')
+        self.x3_ok[nat.IN_DENSE] = True   # the chain's x3 kernel (its split-row instantiation) ran
+        return True
 
     def __call__(self, rows: int, out: torch.Tensor, in0: torch.Tensor, w0: int,
                  mode: int = nat.IN_DENSE, in1=None, w1: int = 0, in2=None, w2: int = 0,
@@ -1034,14 +1062,17 @@ class ConvPlan:
         nat.check(rc, 'rg_conv_proj_x3')
         return True
 
-    def run_x3(self, x, e, g, x_out, pq, nxt=None, pq_out=None) -> bool:
+    def run_x3(self, x, e, g, x_out, pq, nxt=None, pq_out=None, e_split=False) -> bool:
         """One rg_conv_layer_x3_for call; with nxt (the next ConvPlan, also x3) it also writes
-        the next layer's P | Q into pq_out (under 'h2' in the units of nxt's W_e image)."""
+        the next layer's P | Q into pq_out (under 'h2' in the units of nxt's W_e image).
+        e_split: e holds split rows (rg_conv_layer_x3_split_for); a False return then says
+        nothing about the layer on float32 rows (fused_ok is left as it was)."""
         lib = nat.lib()
         st = nat.stream_ptr(x.device)
         ws = self.workspace(lib.rg_conv_layer_x3_workspace_size(g.n_nodes), st)
         tbl = g.conv_x3_blocks()
-        rc = lib.rg_conv_layer_x3_for(
+        call = lib.rg_conv_layer_x3_split_for if e_split else lib.rg_conv_layer_x3_for
+        rc = call(
             self._layers(), nxt._layers(4) if nxt is not None else None,
             nxt._layers() if nxt is not None else None,
             nat.REDUCE[self.aggr], x.data_ptr(), x.stride(0), e.data_ptr(), e.stride(0),
@@ -1049,7 +1080,8 @@ class ConvPlan:
             x_out.data_ptr(), x_out.stride(0), nat.ptr(pq_out),
             tbl.data_ptr() if tbl is not None else None, ws.data_ptr(), ws.numel(), st)
         if rc == nat.RG_ERR_UNSUPPORTED:
-            self.fused_ok = False
+            if not e_split:
+                self.fused_ok = False
             return False
         nat.check(rc, 'rg_conv_layer_x3')
         self.fused_ok = True
@@ -1263,8 +1295,19 @@ def forward_batched(plans: ModelPlans, node_feats: torch.Tensor, edge_feats_dst:
     mark('edge_encoder:start', True)
     Ce = plans.edge_enc.out_dim
     e = alloc('e', (Ecap, Ce), T)
-    plans.edge_enc(Ecap, e, edge_feats_dst, edge_feats_dst.shape[1], rows_dev=ne_dev,
-                   segs=segs('edge'))
+
+    def encode_edges():
+        plans.edge_enc(Ecap, e, edge_feats_dst, edge_feats_dst.shape[1], rows_dev=ne_dev,
+                       segs=segs('edge'))
+    # e as split rows (E_SPLIT) when every conv layer will read them: 'h2', every layer on the
+    # fused x3 path and its one-wave edge launch (centred images -- the fused x3 set always
+    # is -- and fewer than 2**22 nodes)
+    e_split = (E_SPLIT and X3_TERMS == 'h2' and len(plans.convs) > 0 and N < (1 << 22)
+               and not plans.frame_norm and all(cv.x3_ready(x, e) for cv in plans.convs)
+               and plans.edge_enc.run_split(Ecap, e, edge_feats_dst, edge_feats_dst.shape[1],
+                                            rows_dev=ne_dev))
+    if not e_split:
+        encode_edges()
     mark('edge_encoder:end', True)
     mark('conv_stack:start', True)
     n_fused = 0
@@ -1291,7 +1334,14 @@ def forward_batched(plans: ModelPlans, node_feats: torch.Tensor, edge_feats_dst:
                 if pq_next.data_ptr() == pq.data_ptr():
                     pq_next = alloc('pq0', (N, 256), torch.float32)
             mark('conv_fused:start')
-            if cv.run_x3(x, e, g, xn, pq, nxt, pq_next):
+            ok = cv.run_x3(x, e, g, xn, pq, nxt, pq_next, e_split)
+            if not ok and e_split:
+                # the layer declined split rows: e once more as float32, for this layer and
+                # every later one (no kernel that expects floats ever sees split rows)
+                encode_edges()
+                e_split = False
+                ok = cv.run_x3(x, e, g, xn, pq, nxt, pq_next)
+            if ok:
                 mark('conv_fused:end')
                 n_fused += 1
                 pq = pq_next
@@ -1300,6 +1350,9 @@ def forward_batched(plans: ModelPlans, node_feats: torch.Tensor, edge_feats_dst:
             if events and not coarse:
                 events.pop()
             pq = None
+        if e_split:   # off the x3 path after all: every other path reads float32 rows
+            encode_edges()
+            e_split = False
         mark('conv_fused:start')
         fused = cv.run_fused(x, e, g, xn)
         if fused:

@@ -375,6 +375,20 @@ int rg_mlp_chain_x3(const rg_layer* layers_host, int n_layers, long rows, const 
                     int in_mode, const float* in0, int ld0, int w0, const int* idx0,
                     const int* idx1, float* out, int ld_out, void* stream);
 
+/* The same chain with its output written as SPLIT ROWS: each row of 64 values v keeps its 256
+ * bytes, and each aligned 32-byte group of eight values (features 8j .. 8j + 7) holds the
+ * eight fp16 heads a0 = fp16(v), 16 bytes, then the eight fp16 residues a1 = fp16(v - a0),
+ * 16 bytes -- the two h2 terms of the row, bit for bit what an RG_LAYER_H2 kernel forms when
+ * it reads the float32 row (csrc/pack_layout.h: split_row_head / split_row_res).  For rows
+ * that several h2 launches read unchanged (the edge rows of a stack of conv layers,
+ * rg_conv_layer_x3_split_for): the split is done once by the writer.  RG_ERR_ARG, launching
+ * nothing, unless every layer is RG_LAYER_H2, the last out_dim and ld_out are both 64 and
+ * out is 16-byte aligned; RG_ERR_UNSUPPORTED for shapes without an instantiation (compiled:
+ * the 7 -> 256 -> 128 -> 128 -> 64 edge encoder) and as rg_mlp_chain_x3. */
+int rg_mlp_chain_x3_split(const rg_layer* layers_host, int n_layers, long rows, const int* rows_dev,
+                          int in_mode, const float* in0, int ld0, int w0, const int* idx0,
+                          const int* idx1, void* out, int ld_out, void* stream);
+
 /* One v_mfma_f32_32x32x16_f16 as the RG_PACK_H2 kernels issue it (one wave, zero
  * accumulators): c[m][n] = sum_k a[m][k] b[n][k] with a, b fp16 bit patterns, row-major
  * [32][16], and c float32 [32][32].  The h2 arithmetic rests on fp16 SUBNORMAL operands
@@ -460,6 +474,18 @@ int rg_conv_layer_x3_for(const rg_layer* layers, const rg_layer* next_pq, const 
                          const float* pq, const int* seg_ptr, const int* src, const int* dst,
                          int n_nodes, float* x_out, int ld_out, float* pq_out, const int* table,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* rg_conv_layer_x3_for over edge rows given as SPLIT ROWS (rg_mlp_chain_x3_split): the edge
+ * launch feeds the loaded halves to its first layer without converting them.  Results are
+ * bit-identical to rg_conv_layer_x3_for on the float32 rows.  RG_ERR_ARG, launching nothing,
+ * unless the images are RG_LAYER_H2, lde is 64 and e_split is 16-byte aligned;
+ * RG_ERR_UNSUPPORTED, launching nothing, where the layer would not run the one-wave edge
+ * launch (layers not packed centred, or n_nodes >= 2^22): hand such layers float32 rows. */
+int rg_conv_layer_x3_split_for(const rg_layer* layers, const rg_layer* next_pq,
+                               const rg_layer* next_we, int aggr, const float* x, int ldx,
+                               const void* e_split, int lde, const float* pq, const int* seg_ptr,
+                               const int* src, const int* dst, int n_nodes, float* x_out,
+                               int ld_out, float* pq_out, const int* table, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* One fused residual_graph_conv_block (gnn_blocks.py:96-113) for the shipped
  * widths (node / edge channels 64, msg MLP 192->128->64, update 128->64, all with
