@@ -16,6 +16,10 @@ pipeline.RadarGNNPipeline.
 Evaluation on the device (import from ``.evaluation``): evaluation.DetectionEvaluator
 (performance_eval_detection.ipynb: confusion matrix, precision, recall) and
 evaluation.SegmentationEvaluator (performance_eval_segmentation.ipynb).
+A sequence on the device (import from ``.sequence``): sequence.SequenceStore holds a
+RadarScenes sequence in HBM and cuts batches of sliding windows there (read_data.py's
+get_sequence_data + extract_frame); evaluation.evaluate_sequence runs every window of a
+sequence to the evaluators' count matrices.
 Object stage on the device (import from ``.objects``): objects.object_list (process_frame's
 numbers), objects.classifier_inputs (the classifier's training_data from the detector's
 clusters) and objects.classify_proposals (detector -> classifier, no host loop).

@@ -71,6 +71,20 @@ class rg_loss_args(ctypes.Structure):
                 ('w_edge_cls', ctypes.c_float), ('w_obj_cls', ctypes.c_float)]
 
 
+class rg_sequence(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in (
+        'scenes', 'mount', 'odometry', 'x_cc', 'y_cc', 'azimuth_sc', 'vr', 'vr_compensated',
+        'rcs', 'timestamp', 'sensor_id', 'label_id', 'track_key')] + [
+        (k, ctypes.c_int) for k in ('n_scenes', 'n_sensors', 'n_odometry', 'n_meas', 'n_tracks')]
+
+
+class rg_window_batch(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in (
+        'scan_ptr', 'scan_ref', 'win_ptr', 'mount', 'odometry', 'meas_scan', 'src_row', 'x_cc',
+        'y_cc', 'azimuth_sc', 'vr', 'vr_compensated', 'rcs', 'timestamp', 'sensor_id',
+        'label_id', 'track_key')]
+
+
 LR_MILESTONES_MAX = 16
 
 
@@ -119,6 +133,9 @@ _SIGNATURES = {
     'rg_frontend_select_workspace_size': (_S, [_I]),
     'rg_frontend_select': (_I, [_P, _P, _P, _I, _F, _F, _F, _F, _F, _P, _I, _P, _P, _P, _P, _S,
                                 _P]),
+    # sequence store (sequence.hip)
+    'rg_sequence_windows': (_I, [ctypes.POINTER(rg_sequence), _P, _I, _I, _L,
+                                 ctypes.POINTER(rg_window_batch), _P]),
     'rg_proposal_centres': (_I, [_P, _I, _P, _I, _I, _F, _F, _F, _F, _P, _P, _P]),
     'rg_cluster_radius_workspace_size': (_S, [_I, _I, _I]),
     'rg_cluster_radius': (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _S, _P]),

@@ -498,3 +498,73 @@ class SegmentationEvaluator(_Counters):
         out.update(segmentation_report(out['confusion_matrix'], out['gt_count_matrix'],
                                        invalid_class_index))
         return out
+
+
+# ------------------------------------------------------------------------- a whole sequence
+def evaluate_window_batch(win, model, cfg, detection: Optional[DetectionEvaluator] = None,
+                          segmentation: Optional[SegmentationEvaluator] = None,
+                          dtype: str = 'fp32', reject_outlier_by_ransac: bool = False,
+                          cache: Optional[dict] = None):
+    """One batch of windows (a batch ``frontend.ScanWindow``) through the front-end, the graph
+    build, the detector's proposal forward and the evaluators' ``update``: what the notebooks
+    do per frame (performance_eval_detection.ipynb, performance_eval_segmentation.ipynb),
+    for every window of the batch at once.  ``model`` is a ``Model_Inference`` with its
+    proposal parameters set; ``cache`` keeps workspaces and buffers between batches.  Returns
+    the batch's FrameBatch (``frontend.frame_batch``) and the forward's outputs (None for a
+    batch without a frame of more than one node)."""
+    torch = _torch()
+    from . import engine, frontend
+    from .graph_features import build_graph_batch
+    if not getattr(model, 'extract_proposals', False):
+        raise ValueError('the detector has no proposal branch: set_param_for_proposal_extraction')
+    cache = cache if cache is not None else {}
+    dd, gd = frontend.dynamic_frame(win, reject_outlier_by_ransac, with_keys=True)
+    fb = frontend.frame_batch(dd, gd)
+    if fb.n_frames == 0:
+        return fb, None
+    gb = build_graph_batch(fb, cfg, ws_cache=cache.setdefault('graph', {}))
+    g = gb.graph
+    other_xy = torch.stack((fb.arrays['meas_px'], fb.arrays['meas_py']), dim=-1)
+
+    def clusters_fn(node_reg, link_cls):
+        return engine.propose_clusters(
+            node_reg, other_xy, fb.frame_ptr, fb.frame_sizes, model.reg_mu, model.reg_sigma,
+            model.clustering_eps, from_links=model.compute_adj_mat_from_links, g=g,
+            link_cls=link_cls, ws_cache=cache.setdefault('proposals', {}))
+
+    with torch.no_grad():
+        out = engine.forward_batched(model.plans(dtype), gb.node_features, gb.edge_features, g,
+                                     None, None, 0, n_pairs_cap=gb.capacity // 2 + 1,
+                                     buffers=cache.setdefault('buffers', {}),
+                                     clusters_fn=clusters_fn)
+    gt_class = fb.labels['class_labels']
+    if detection is not None:
+        detection.update(out.node_cls, out.obj_cls, out.cluster_ptr, out.cluster_idx, gt_class,
+                         fb.track_key, fb.frame_ptr, max_frame_nodes=max(fb.frame_sizes))
+    if segmentation is not None:
+        segmentation.update(out.node_cls, gt_class)
+    return fb, out
+
+
+def evaluate_sequence(store, model, cfg, window_size: int = 10, batch_windows: int = 64,
+                      dtype: str = 'fp32', detection: Optional[DetectionEvaluator] = None,
+                      segmentation: Optional[SegmentationEvaluator] = None,
+                      reject_outlier_by_ransac: bool = False):
+    """Every sliding window of a ``sequence.SequenceStore`` to the notebooks' count matrices:
+    per batch of ``batch_windows`` consecutive sliding positions ``store.windows`` ->
+    ``evaluate_window_batch``.  No host work per window; per batch the host waits only where
+    ``frontend.select_dynamic`` and ``engine.propose_clusters`` already do and for the one
+    ``frame_ptr`` read of ``frontend.frame_batch``.  Returns (detection, segmentation), new
+    evaluators unless given; their ``result()`` is the only read of the counters."""
+    if int(batch_windows) < 1:
+        raise ValueError(f'batch_windows={batch_windows} < 1')
+    detection = detection if detection is not None else DetectionEvaluator(int(cfg.num_classes))
+    segmentation = (segmentation if segmentation is not None
+                    else SegmentationEvaluator(int(cfg.num_classes)))
+    n = store.n_windows(window_size)
+    cache: dict = {}
+    for i0 in range(0, n, int(batch_windows)):
+        win = store.windows(range(i0, min(i0 + int(batch_windows), n)), window_size)
+        evaluate_window_batch(win, model, cfg, detection, segmentation, dtype,
+                              reject_outlier_by_ransac, cache)
+    return detection, segmentation

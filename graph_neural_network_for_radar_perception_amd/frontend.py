@@ -16,10 +16,14 @@ followed by the RANSAC rejection of meas_selection.py:96-166: the host draws the
 sets exactly as the reference does -- ``np.random.shuffle`` on numpy's global generator,
 scans in window order -- and ``rg_frontend_gate_lists`` / ``rg_frontend_ransac`` evaluate
 every set on the device, so a seeded generator reproduces the reference's flags.
+
+Windows come from host arrays (``ScanWindow.from_numpy``, ``scan_window_batch``) or, for a
+whole sequence, from ``sequence.SequenceStore.windows``; ``frame_batch`` hands the dynamic
+frames of a batch of windows to the graph build.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -204,12 +208,15 @@ def compute_ground_truth(d: dict) -> dict:
     return {'offsetx': ox, 'offsety': oy, 'class_labels': cls}
 
 
-def select_dynamic(d: dict, gt: dict, grid_limits=GRID_LIMITS) -> Tuple[dict, dict]:
+def select_dynamic(d: dict, gt: dict, grid_limits=GRID_LIMITS,
+                   with_keys: bool = False) -> Tuple[dict, dict]:
     """select_meas_within_the_grid then select_moving_data, one order-preserving
     compaction (rg_frontend_select) and a gather of every field.  Synchronises once (the
     selected count sizes the outputs, as the reference's boolean indexing does).  For a
     batch of windows the returned data dict also holds 'frame_ptr' (int32, device): the
-    dynamic frame of each window, ready for the batched graph build."""
+    dynamic frame of each window, ready for the batched graph build.  ``with_keys`` adds
+    'track_key' (int32: the selected measurements' track keys, 0 = no track -- what
+    evaluation.DetectionEvaluator.update groups the ground-truth clusters by)."""
     lib = nat.lib()
     px = d['meas_px']
     dev = px.device
@@ -231,14 +238,62 @@ def select_dynamic(d: dict, gt: dict, grid_limits=GRID_LIMITS) -> Tuple[dict, di
     dd = {key: v.index_select(0, sel) for key, v in d.items()
           if isinstance(v, torch.Tensor) and not key.startswith('_')}
     gd = {key: v.index_select(0, sel) for key, v in gt.items()}
+    if with_keys:
+        dd['track_key'] = d['_track_key'].index_select(0, sel)
     if fptr is not None:
         dd['frame_ptr'] = fptr
     return dd, gd
 
 
-def dynamic_frame(w: ScanWindow, reject_outlier_by_ransac: bool = False) -> Tuple[dict, dict]:
+def dynamic_frame(w: ScanWindow, reject_outlier_by_ransac: bool = False,
+                  with_keys: bool = False) -> Tuple[dict, dict]:
     """The whole front-end for one window: (data_dict_dyn, node_labels_dict_dyn) of
-    datagen_gnn.RadarScenesDataset.__getitem__ (datagen_gnn.py:96-102)."""
+    datagen_gnn.RadarScenesDataset.__getitem__ (datagen_gnn.py:96-102).  ``with_keys``: as
+    select_dynamic's."""
     d = extract_and_sync_radar_data(w, reject_outlier_by_ransac)
     gt = compute_ground_truth(d)
-    return select_dynamic(d, gt)
+    return select_dynamic(d, gt, with_keys=with_keys)
+
+
+def frame_batch(dd: dict, gd: Optional[dict] = None):
+    """The dynamic frames of a batch of windows (select_dynamic's data dict, with its
+    'frame_ptr') as the ``graph_features.FrameBatch`` that ``build_graph_batch`` takes.  One
+    host read (frame_ptr, for frame_sizes).  The cluster CSR is empty: the proposal branch
+    supplies the clusters.  Frames with <= 1 node leave the batch with their nodes -- the
+    reference never runs them (datagen_gnn.py:104, segmentation_accuracy.py:44-45, 81-83).
+
+    Besides FrameBatch's own fields the batch carries ``windows`` (the kept frames' slots
+    in the batch of windows), ``track_key`` (the kept nodes' keys when ``dd`` has them, else
+    None) and ``labels`` (``gd``'s tensors for the kept nodes, None without ``gd``)."""
+    from .graph_features import FrameBatch
+    fptr = dd['frame_ptr']
+    dev = fptr.device
+    fp = fptr.cpu().numpy().astype(np.int64)
+    sizes = np.diff(fp)
+    kept = np.flatnonzero(sizes > 1)
+    arrays = {k: v for k, v in dd.items() if k.startswith('meas_')}
+    key = dd.get('track_key')
+    labels = dict(gd) if gd is not None else None
+    if kept.size < sizes.size:
+        # the dropped frames hold at most one node each: kept row p is row p + (the dropped
+        # rows at or before it), a search over the few dropped positions
+        drop = fp[:-1][sizes == 1]
+        n_kept = int(fp[-1]) - int(drop.size)
+        if drop.size:
+            adj = torch.from_numpy(drop - np.arange(drop.size))
+            adj = (adj.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda'
+                   else adj.to(dev))
+            p = torch.arange(n_kept, dtype=torch.int64, device=dev)
+            sel = p + torch.searchsorted(adj, p, right=True)
+            arrays = {k: v.index_select(0, sel) for k, v in arrays.items()}
+            key = key.index_select(0, sel) if key is not None else None
+            if labels is not None:
+                labels = {k: v.index_select(0, sel) for k, v in labels.items()}
+        new_fp = np.concatenate(([0], np.cumsum(sizes[kept]))).astype(np.int32)
+        fptr = torch.from_numpy(new_fp)
+        fptr = (fptr.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda'
+                else fptr.to(dev))
+    i32 = dict(dtype=torch.int32, device=dev)
+    return FrameBatch(arrays, fptr, [int(s) for s in sizes[kept]], torch.zeros(1, **i32),
+                      torch.zeros(1, **i32), 0, windows=[int(w) for w in kept], track_key=key,
+                      labels=labels).mark_ready()

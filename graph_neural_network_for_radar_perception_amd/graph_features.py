@@ -146,6 +146,12 @@ class FrameBatch:
     # recorded on the producing stream once every array above is written (uploads, or device
     # ops of the caller): consumers on other streams wait on it (pipeline.PipelinedSteps)
     ready: Optional['torch.cuda.Event'] = None
+    # batches made by frontend.frame_batch: the kept frames' slots in the batch of windows,
+    # the nodes' track keys (int32, 0 = no track) and ground-truth tensors (class_labels,
+    # offsetx, offsety) -- what the evaluators read beside the forward's outputs
+    windows: Optional[List[int]] = None
+    track_key: Optional[torch.Tensor] = None
+    labels: Optional[dict] = None
 
     def tensors(self) -> List[torch.Tensor]:
         return list(self.arrays.values()) + [self.frame_ptr, self.cluster_ptr, self.cluster_idx]

@@ -242,3 +242,34 @@ def make_scan_window(seed: int, n_scans: int = 10, mean_meas: int = 160) -> dict
         yaw += yr * dt
     out.update(n_scans=n_scans, scan_ptr=ptr, mount=mount, odometry=odo, track_id_bytes=tid)
     return out
+
+
+def make_sequence(seed: int, n_scenes: int, mean_meas: int = 134):
+    """A synthetic RadarScenes sequence, the inputs of ``sequence.SequenceStore.from_numpy``:
+    ``make_scan_window``'s scans as the scenes of one sequence, with the files' dtypes
+    (sensor_id / label_id uint8, track_id byte strings).  mean_meas = 134 is sequence_148's
+    mean scene size (803,760 measurements in 6,011 scenes).  Returns (radar_data dict,
+    odometry structured array, the five scene lists, sensors)."""
+    w = make_scan_window(seed, n_scans=n_scenes, mean_meas=mean_meas)
+    ptr = np.asarray(w['scan_ptr'])
+    radar = {k: w[k] for k in ('x_cc', 'y_cc', 'azimuth_sc', 'vr', 'vr_compensated', 'rcs',
+                               'timestamp')}
+    radar['sensor_id'] = w['sensor_id'].astype(np.uint8)
+    radar['label_id'] = w['label_id'].astype(np.uint8)
+    radar['track_id'] = w['track_id_bytes'].astype('S32')
+    odo = np.zeros(n_scenes, dtype=[('timestamp', '<i8'), ('x_seq', '<f8'), ('y_seq', '<f8'),
+                                    ('yaw_seq', '<f8'), ('vx', '<f8'), ('yaw_rate', '<f8')])
+    for c, k in enumerate(('x_seq', 'y_seq', 'yaw_seq', 'vx', 'yaw_rate')):
+        odo[k] = w['odometry'][:, c]
+    first = ptr[:-1]
+    ts = [int(v) for v in w['timestamp'][first]]
+    odo['timestamp'] = ts
+    sid = [int(v) for v in w['sensor_id'][first]]
+    sensors = {}
+    for s, i in enumerate(sid):
+        x, y, yaw = (float(v) for v in w['mount'][s])
+        sensors[f'radar_{i}'] = {'id': i, 'x': x, 'y': y, 'yaw': yaw}
+    lists = {'current_timestamps': ts, 'radar_id': sid, 'odometry_timestamp': ts,
+             'odometry_index': list(range(n_scenes)),
+             'radar_data_indices': [[int(a), int(b)] for a, b in zip(ptr[:-1], ptr[1:])]}
+    return radar, odo, lists, sensors

@@ -759,6 +759,75 @@ int rg_frontend_select(const float* px, const float* py, const float* cls, int n
                        const int* win_ptr, int n_windows, int* frame_ptr, int* index,
                        int* n_selected, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------ sequence store */
+
+/* A RadarScenes sequence resident in device memory (sequence.py, SequenceStore): what
+ * read_data.get_sequence_data (read_data.py:416-439) returns, uploaded once.  scenes: int32
+ * [n_scenes][4] in chain order = (begin, end) of the scene's rows in the measurement arrays
+ * (radar_indices; may be empty, need not be contiguous or ascending), its row of the mount
+ * table and its row of the odometry table.  mount: f64 [n_sensors][3] (x, y, yaw); odometry:
+ * f64 [n_odometry][5] (x_seq, y_seq, yaw_seq, vx, yaw_rate).  Measurement arrays of n_meas
+ * rows: six f32 fields, timestamp int64, sensor_id / label_id u8 (as the .h5 files hold them),
+ * track_key int32 (0 = the empty track id, else 1..n_tracks). */
+typedef struct rg_sequence {
+  const int* scenes;
+  const double* mount;
+  const double* odometry;
+  const float* x_cc;
+  const float* y_cc;
+  const float* azimuth_sc;
+  const float* vr;
+  const float* vr_compensated;
+  const float* rcs;
+  const int64_t* timestamp;
+  const uint8_t* sensor_id;
+  const uint8_t* label_id;
+  const int* track_key;
+  int n_scenes, n_sensors, n_odometry, n_meas, n_tracks;
+} rg_sequence;
+
+/* The windows cut from a sequence, the batch layout of rg_frontend_sync: n_windows * W
+ * window-scans j = b * W + w.  scan_ptr int32 [n_windows * W + 1], scan_ref int32
+ * [n_windows * W] (the window's last scan), win_ptr int32 [n_windows + 1], mount f64
+ * [n_windows * W][3], odometry f64 [n_windows * W][5]; per output measurement (capacity rows
+ * each) meas_scan int32 (its window-scan), src_row int32 (its row in the sequence), the six
+ * f32 fields, timestamp, sensor_id and label_id int64, track_key int32. */
+typedef struct rg_window_batch {
+  int* scan_ptr;
+  int* scan_ref;
+  int* win_ptr;
+  double* mount;
+  double* odometry;
+  int* meas_scan;
+  int* src_row;
+  float* x_cc;
+  float* y_cc;
+  float* azimuth_sc;
+  float* vr;
+  float* vr_compensated;
+  float* rcs;
+  int64_t* timestamp;
+  int64_t* sensor_id;
+  int64_t* label_id;
+  int* track_key;
+} rg_window_batch;
+
+/* create_dataset_sliding_window + the slicing of extract_and_sync_radar_data
+ * (read_data.py:203-224, 250-291) for a batch of windows, on the device: window b holds the
+ * W scenes win_first[b] .. win_first[b] + W - 1 (win_first: int32 [n_windows], device;
+ * repeats and overlaps allowed).  Two launches, no host synchronisation: a one-workgroup
+ * scan of the n_windows * W scene sizes writes the per-window-scan outputs, then one wave per
+ * window-scan copies its rows: output row m of window-scan j comes from sequence row
+ * scenes[s][0] + (m - scan_ptr[j]); its key is k == 0 ? 0 : k + b * n_tracks (the same track
+ * in two windows of a batch stays two tracks).  capacity = the rows the per-measurement
+ * outputs hold (the host's sum of the scene sizes): rows at or beyond it, or beyond the
+ * computed scan_ptr[n_windows * W], are never written, and a scene range is cut to
+ * [0, n_meas) before it is read; a window-scan whose scene, sensor row or odometry row lies
+ * outside its table is empty with a NaN pose.  RG_ERR_ARG, launching nothing: a NULL
+ * pointer, a negative size, W < 1, n_windows * W or n_windows * n_tracks beyond int32. */
+int rg_sequence_windows(const rg_sequence* seq, const int* win_first, int n_windows, int W,
+                        long capacity, const rg_window_batch* out, void* stream);
+
 /* ------------------------------------------------------------ proposal branch */
 
 /* Predicted cluster centres (gnn_detector.py:164-167): unnormalize_gt_offsets
