@@ -136,6 +136,11 @@ _SIGNATURES = {
     # sequence store (sequence.hip)
     'rg_sequence_windows': (_I, [ctypes.POINTER(rg_sequence), _P, _I, _I, _L,
                                  ctypes.POINTER(rg_window_batch), _P]),
+    # training feed (training_feed.hip)
+    'rg_frontend_flip': (_I, [_P, _P, _P, _I, _P, _I, _P]),
+    'rg_train_labels': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P]),
+    'rg_train_offsets_workspace_size': (_S, [_I]),
+    'rg_train_offsets': (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _S, _P]),
     'rg_proposal_centres': (_I, [_P, _I, _P, _I, _I, _F, _F, _F, _F, _P, _P, _P]),
     'rg_cluster_radius_workspace_size': (_S, [_I, _I, _I]),
     'rg_cluster_radius': (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _S, _P]),

@@ -88,6 +88,9 @@ class config:
         self.window_size = sel['temporal_window_size']
         self.ball_query_eps_square = sel['ball_query_eps_square']
         self.k_number_nearest_points = sel['k_number_nearest_points']
+        # read by training.train_sequence (datagen_gnn.py:67-68)
+        self.reject_static_meas_by_ransac = bool(sel.get('reject_static_meas_by_ransac', False))
+        self.dataset_augmentation = bool(sel.get('dataset_augmentation', False))
         self.min_x, self.max_x = grid['min_x'], grid['max_x']
         self.min_y, self.max_y = grid['min_y'], grid['max_y']
         # set_config_gnn.py:41-44

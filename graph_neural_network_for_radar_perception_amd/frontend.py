@@ -19,7 +19,9 @@ every set on the device, so a seeded generator reproduces the reference's flags.
 
 Windows come from host arrays (``ScanWindow.from_numpy``, ``scan_window_batch``) or, for a
 whole sequence, from ``sequence.SequenceStore.windows``; ``frame_batch`` hands the dynamic
-frames of a batch of windows to the graph build.
+frames of a batch of windows to the graph build.  For training, ``flip_along_x`` applies the
+x-axis flip augmentation of get_data_for_datagen (read_data.py:522-524) per window, with the
+flags ``draw_flips`` takes from numpy's global generator (datagen_gnn.py:92-94).
 """
 from __future__ import annotations
 
@@ -189,8 +191,11 @@ def _ransac(w: ScanWindow, st: torch.Tensor):
     return ratio, valid.bool()
 
 
-def compute_ground_truth(d: dict) -> dict:
-    """compute_node_labels.compute_ground_truth: class_labels, offsetx, offsety (f32)."""
+def compute_ground_truth(d: dict, numpy_mean: bool = False) -> dict:
+    """compute_node_labels.compute_ground_truth: class_labels, offsetx, offsety (f32).  The
+    offsets are taken to a track mean made in float64 (within an ulp of the reference's);
+    ``numpy_mean`` retakes them with numpy's own float32 mean (rg_train_offsets), bit for bit
+    the reference's -- what the training labels are made from."""
     lib = nat.lib()
     px = d['meas_px']
     dev = px.device
@@ -205,6 +210,12 @@ def compute_ground_truth(d: dict) -> dict:
         d['_stationary_u8'].data_ptr(), o2n.data_ptr(), int(o2n.numel()), px.data_ptr(),
         d['meas_py'].data_ptr(), n, cls.data_ptr(), ox.data_ptr(), oy.data_ptr(),
         ws.data_ptr(), ws.numel(), nat.stream_ptr(dev)), 'rg_frontend_labels')
+    if numpy_mean:
+        ws = torch.empty(lib.rg_train_offsets_workspace_size(nt), dtype=torch.uint8, device=dev)
+        nat.check(lib.rg_train_offsets(
+            d['_track_key'].data_ptr(), nt, px.data_ptr(), d['meas_py'].data_ptr(), n,
+            ox.data_ptr(), oy.data_ptr(), ws.data_ptr(), ws.numel(), nat.stream_ptr(dev)),
+            'rg_train_offsets')
     return {'offsetx': ox, 'offsety': oy, 'class_labels': cls}
 
 
@@ -245,13 +256,54 @@ def select_dynamic(d: dict, gt: dict, grid_limits=GRID_LIMITS,
     return dd, gd
 
 
+def draw_flips(n: int) -> np.ndarray:
+    """The flip decisions of ``n`` successive RadarScenesDataset.__getitem__ calls
+    (datagen_gnn.py:92-94, ``np.random.rand() >= 0.5`` each) as a bool array, drawn from
+    numpy's global generator as ``_ransac`` draws its consensus sets: ``np.random.rand(n)``
+    takes the same ``n`` doubles from the stream as ``n`` single calls and leaves the generator
+    in the same state, so a seeded generator reproduces the reference's single-worker dataset
+    order.  (With the RANSAC rejection on, the reference interleaves each window's shuffles
+    with its flip draw; here a batch's flips are drawn first.)"""
+    return np.random.rand(int(n)) >= 0.5
+
+
+def flip_along_x(d: dict, flags) -> dict:
+    """The x-axis flip augmentation of get_data_for_datagen (read_data.py:522-524) on
+    ``extract_and_sync_radar_data``'s dict, in place (rg_frontend_flip): meas_py and meas_vy
+    negated for the windows whose flag is set.  ``flags``: one uint8 / bool entry per window,
+    a host array (uploaded asynchronously) or a device tensor.  It belongs between the sync
+    and ``compute_ground_truth`` / ``select_dynamic``, where the reference flips.  No host
+    synchronisation."""
+    py, vy = d['meas_py'], d['meas_vy']
+    dev = py.device
+    nw = int(d.get('_n_windows', 1))
+    if isinstance(flags, torch.Tensor):
+        f = flags.to(device=dev, dtype=torch.uint8).reshape(-1).contiguous()
+    else:
+        f = torch.from_numpy(np.ascontiguousarray(np.asarray(flags).reshape(-1) != 0,
+                                                  dtype=np.uint8))
+        f = f.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda' else f.to(dev)
+    if int(f.shape[0]) != nw:
+        raise ValueError(f'{int(f.shape[0])} flip flags for {nw} windows')
+    nat.check(nat.lib().rg_frontend_flip(py.data_ptr(), vy.data_ptr(), nat.ptr(d.get('_win_ptr')),
+                                         nw, f.data_ptr(), int(py.shape[0]),
+                                         nat.stream_ptr(dev)), 'rg_frontend_flip')
+    return d
+
+
 def dynamic_frame(w: ScanWindow, reject_outlier_by_ransac: bool = False,
-                  with_keys: bool = False) -> Tuple[dict, dict]:
+                  with_keys: bool = False, flip=None,
+                  numpy_mean: Optional[bool] = None) -> Tuple[dict, dict]:
     """The whole front-end for one window: (data_dict_dyn, node_labels_dict_dyn) of
     datagen_gnn.RadarScenesDataset.__getitem__ (datagen_gnn.py:96-102).  ``with_keys``: as
-    select_dynamic's."""
+    select_dynamic's.  ``flip``: ``flip_along_x``'s per-window flags, applied between the sync
+    and the ground truth (None: no flip).  ``numpy_mean``: compute_ground_truth's; by default
+    on with ``flip`` given (the training feed, all-zero flags included) and off without, which
+    is the path as it was."""
     d = extract_and_sync_radar_data(w, reject_outlier_by_ransac)
-    gt = compute_ground_truth(d)
+    if flip is not None:
+        flip_along_x(d, flip)
+    gt = compute_ground_truth(d, flip is not None if numpy_mean is None else bool(numpy_mean))
     return select_dynamic(d, gt, with_keys=with_keys)
 
 

@@ -30,6 +30,7 @@ import ctypes
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 
 from . import _native as nat
@@ -995,6 +996,51 @@ def broadcast_parameters(flat: torch.Tensor, world: int, src: int = 0):
         dist.broadcast(flat, src)
 
 
+# ------------------------------------------------------------------ labels on the device
+def training_labels(batch, gb, cfg, ws_cache: Optional[dict] = None) -> dict:
+    """The labels of RadarScenesDataset.__getitem__ (datagen_gnn.py:126-139) for a batch of
+    dynamic frames, on the device and without a host synchronisation.  ``batch``: a
+    ``frontend.frame_batch(dd, gd)`` batch that carries ``track_key`` and ``labels``; ``gb``:
+    the ``GraphBatch`` built from it.  One rg_train_labels launch writes node_class (int64
+    [N]), node_offsets (f32 [N, 2]) and edge_class (int64 [pair capacity] in link-pair order,
+    0 past the graph's pair count); ``evaluation.gt_clusters`` gives the ground-truth clusters
+    of compute_node_idx_for_each_cluster.  Returns the dict ``TrainEngine.forward`` takes --
+    those three, cluster_labels (the clusters' classes) and class_weights
+    (cfg.class_weights_dyn) -- plus cluster_ptr, cluster_idx and n_clusters_dev (int32 [1])."""
+    from .evaluation import gt_clusters
+    if batch.track_key is None or batch.labels is None:
+        raise ValueError('training_labels needs a frame_batch(dd, gd) batch made with_keys=True')
+    g = gb.graph
+    N = int(batch.n_nodes)
+    key = batch.track_key
+    dev = key.device
+    gd = {k: _f32(batch.labels[k]).contiguous() for k in ('class_labels', 'offsetx', 'offsety')}
+    if int(key.shape[0]) != N or any(int(v.shape[0]) != N for v in gd.values()):
+        raise ValueError(f'the batch has {N} nodes; its keys / labels do not')
+    if key.dtype != torch.int32:
+        raise TypeError(f'track_key must be int32; got {key.dtype}')
+    cap = int(g.pair_src.shape[0])
+    node_class = torch.empty(max(N, 1), dtype=torch.int64, device=dev)
+    node_offsets = torch.empty((max(N, 1), 2), dtype=torch.float32, device=dev)
+    edge_class = torch.empty(cap, dtype=torch.int64, device=dev)
+    nat.check(nat.lib().rg_train_labels(
+        gd['class_labels'].data_ptr(), gd['offsetx'].data_ptr(), gd['offsety'].data_ptr(), N,
+        key.contiguous().data_ptr(), g.pair_src.data_ptr(), g.pair_dst.data_ptr(),
+        g.n_pairs_dev.data_ptr(), cap, node_class.data_ptr(), node_offsets.data_ptr(),
+        edge_class.data_ptr(), nat.stream_ptr(dev)), 'rg_train_labels')
+    node_class, node_offsets = node_class[:N], node_offsets[:N]
+    gt = gt_clusters(key, node_class, batch.frame_ptr, ws_cache)
+    cache = ws_cache if ws_cache is not None else {}
+    cw = cache.get(('class_weights', dev))
+    if cw is None:
+        cw = cache[('class_weights', dev)] = torch.tensor(cfg.class_weights_dyn,
+                                                          dtype=torch.float32, device=dev)
+    return {'node_class': node_class, 'node_offsets': node_offsets, 'edge_class': edge_class,
+            'cluster_labels': gt['cluster_class'], 'class_weights': cw,
+            'cluster_ptr': gt['cluster_ptr'], 'cluster_idx': gt['cluster_idx'],
+            'n_clusters_dev': gt['n_clusters']}
+
+
 class RadarGNNTrainer:
     """One data-parallel training iteration (training.py:66-85 for one rank's batch):
     graph build + features (pipeline) -> forward tape + Loss_Graph -> backward ->
@@ -1051,3 +1097,90 @@ class RadarGNNTrainer:
         scale = allreduce_gradients(self.engine.flat_bucket, self.world)
         self.opt.step(self.engine.flat_grad, grad_scale=scale, losses=self.engine.loss_slots)
         return losses, acc, gb
+
+    def step_frames(self, batch, events=None):
+        """``step`` for a ``frontend.frame_batch(dd, gd)`` batch of real frames (made
+        ``with_keys=True``): the graph is built once, ``training_labels`` makes every label
+        and the ground-truth clusters from the batch's keys on the device, and the three host
+        sizes the launches need (edges, pairs, clusters) come back in ONE device-to-host copy.
+        From the forward on it is ``step``, and it returns what ``step`` does: (losses,
+        accuracies, GraphBatch).
+
+        An empty batch -- every window's dynamic frame had <= 1 node, which the reference
+        never trains on (datagen_gnn.py:104, training.py:69): with ``world == 1`` nothing
+        runs and None is returned (no applied step).  With ``world > 1`` the rank still joins
+        the gradient all-reduce, with zero gradients and NaN in its loss slots: the summed
+        loss is NaN on every rank, so the optimizer kernel skips the step everywhere
+        (skip_batch) and no rank waits for a missing peer; None is returned."""
+        from .graph_features import build_graph_batch
+        eng = self.engine
+        if batch.n_frames == 0:
+            if self.world > 1:
+                eng.flat_grad.zero_()
+                eng.loss_slots.fill_(float('nan'))
+                scale = allreduce_gradients(eng.flat_bucket, self.world)
+                self.opt.step(eng.flat_grad, grad_scale=scale, losses=eng.loss_slots)
+            return None
+        gb = build_graph_batch(batch, self.cfg, ws_cache=self.ws_cache)
+        g = gb.graph
+        labels = training_labels(batch, gb, self.cfg, self.ws_cache)
+        sizes = torch.cat((gb.n_edges_dev.reshape(1), g.n_pairs_dev.reshape(1),
+                           labels['n_clusters_dev'].reshape(1))).tolist()
+        g.n_edges, g.n_pairs, ncl = (int(v) for v in sizes)
+
+        def mark(name):
+            if events is not None:
+                ev = torch.cuda.Event(enable_timing=True)
+                ev.record(torch.cuda.current_stream(eng.device))
+                events.append((name, ev))
+
+        mark('train_forward:start')
+        losses, acc, tape = eng.forward(gb.node_features, gb.edge_features, g,
+                                        labels['cluster_ptr'], labels['cluster_idx'], ncl, labels)
+        mark('train_forward:end')
+        mark('train_backward:start')
+        eng.backward(tape, self.ones)
+        mark('train_backward:end')
+        eng.loss_slots.copy_(losses)
+        scale = allreduce_gradients(eng.flat_bucket, self.world)
+        self.opt.step(eng.flat_grad, grad_scale=scale, losses=eng.loss_slots)
+        return losses, acc, gb
+
+
+def train_sequence(store, trainer: RadarGNNTrainer, cfg, indices, window_size: int = 10,
+                   batch_windows: int = 64, augmentation: Optional[bool] = None, on_step=None):
+    """Training from a ``sequence.SequenceStore``: the sliding positions ``indices``, in the
+    caller's order (shuffling is the caller's), in batches of ``batch_windows``; each batch
+    goes ``store.windows`` -> ``frontend.dynamic_frame`` (with the x-axis flip when
+    ``augmentation``, default cfg.dataset_augmentation; the flags come from
+    ``frontend.draw_flips``, numpy's global generator; the offsets always to numpy's float32
+    track mean, ``numpy_mean``) -> ``frontend.frame_batch`` ->
+    ``RadarGNNTrainer.step_frames``.  cfg.reject_static_meas_by_ransac is passed to the
+    front-end.  No host work per window; per batch the host waits only where
+    ``select_dynamic`` (and the RANSAC draws), ``frame_batch`` and ``step_frames`` do.
+    ``on_step(step index, positions, flags or None, step_frames' result)`` is called after
+    every batch.  Returns (losses f32 [steps, 4], accuracies f32 [steps, 3]) on the device, one
+    row per batch that had a frame to train on (a skipped NaN step keeps its row)."""
+    from . import frontend
+    if int(batch_windows) < 1:
+        raise ValueError(f'batch_windows={batch_windows} < 1')
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    augmentation = bool(cfg.dataset_augmentation if augmentation is None else augmentation)
+    ransac = bool(getattr(cfg, 'reject_static_meas_by_ransac', False))
+    losses, accs = [], []
+    for k, i0 in enumerate(range(0, int(idx.shape[0]), int(batch_windows))):
+        pos = idx[i0:i0 + int(batch_windows)]
+        flags = frontend.draw_flips(int(pos.shape[0])) if augmentation else None
+        win = store.windows(pos, window_size)
+        dd, gd = frontend.dynamic_frame(win, ransac, with_keys=True, flip=flags, numpy_mean=True)
+        out = trainer.step_frames(frontend.frame_batch(dd, gd))
+        if out is not None:
+            losses.append(out[0])
+            accs.append(out[1])
+        if on_step is not None:
+            on_step(k, pos, flags, out)
+    dev = trainer.engine.device
+    if not losses:
+        return (torch.empty((0, N_LOSS_SLOTS), dtype=torch.float32, device=dev),
+                torch.empty((0, 3), dtype=torch.float32, device=dev))
+    return torch.stack(losses), torch.stack(accs)

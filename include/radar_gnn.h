@@ -828,6 +828,54 @@ typedef struct rg_window_batch {
 int rg_sequence_windows(const rg_sequence* seq, const int* win_first, int n_windows, int W,
                         long capacity, const rg_window_batch* out, void* stream);
 
+/* ------------------------------------------------------------ training feed */
+
+/* The x-axis flip augmentation of get_data_for_datagen (read_data.py:522-524) for a batch of
+ * windows: py and vy (f32 [n_meas], rg_frontend_sync's outputs) are negated in place over
+ * [win_ptr[w], win_ptr[w + 1]) for every window w with flip[w] != 0 (flip: u8 [n_windows],
+ * device); the other windows' values are not written.  win_ptr == NULL: one window covering
+ * [0, n_meas).  It runs between rg_frontend_sync and rg_frontend_labels / rg_frontend_select,
+ * where the reference flips, so the offsets and the grid test see the flipped values.  One
+ * launch, no host synchronisation; n_meas == 0 or n_windows == 0 launches nothing.
+ * RG_ERR_ARG, launching nothing: a negative size, a NULL pointer with n_meas > 0, or
+ * win_ptr == NULL with n_windows > 1. */
+int rg_frontend_flip(float* py, float* vy, const int* win_ptr, int n_windows,
+                     const uint8_t* flip, int n_meas, void* stream);
+
+/* The label tensors of RadarScenesDataset.__getitem__ (datagen_gnn.py:126-134) for a batch of
+ * dynamic frames, one launch: node_class int64 [n_nodes] from the f32 class_labels,
+ * node_offsets f32 [n_nodes][2] = (offset_x, offset_y) interleaved (8-byte aligned) and
+ * edge_class int64 [pair_capacity], the labels of compute_edge_labels.compute_ground_truth
+ * (compute_edge_labels.py:7-20) in link-pair order: for p < *n_pairs (the device count
+ * rg_link_pairs wrote, cut to pair_capacity) 1 when track_key[pair_src[p]] ==
+ * track_key[pair_dst[p]] and that key is not 0 (no track), else 0; 0 for every p in
+ * [*n_pairs, pair_capacity) and for a pair with an endpoint outside [0, n_nodes).  (The
+ * reference reads the labels at nonzero(triu(adj, 1)) out of a matrix filled over adj_list =
+ * where(adj): every such pair is an edge with src < dst, so no matrix is needed.)  No host
+ * synchronisation; n_nodes == 0 and pair_capacity == 0 launch nothing.  RG_ERR_ARG, launching
+ * nothing: a negative size, n_nodes * 2 or pair_capacity beyond int32, a NULL node array with
+ * n_nodes > 0, a NULL pair array with pair_capacity > 0. */
+int rg_train_labels(const float* class_labels, const float* offset_x, const float* offset_y,
+                    int n_nodes, const int* track_key, const int* pair_src, const int* pair_dst,
+                    const int* n_pairs, long pair_capacity, int64_t* node_class,
+                    float* node_offsets, int64_t* edge_class, void* stream);
+
+/* generate_gt_offset (compute_node_labels.py:50-67) with the mean numpy takes: offset_x[i] =
+ * mean(px of i's track) - px[i] (offset_y alike; 0 where track_key[i] is 0 or outside
+ * [1, n_tracks]), the mean being np.mean of the track's float32 values in measurement order
+ * -- a float32 pairwise sum (numpy's blocks of 128, eight interleaved partial sums) over the
+ * count -- so the offsets equal the reference's bit for bit.  rg_frontend_labels takes the
+ * mean in float64, within an ulp of this one; a training label is compared exactly, so the
+ * training feed overwrites rg_frontend_labels' offsets with these.  It runs after
+ * rg_frontend_flip.  Three launches (first index and count per key, one wave per key for the
+ * mean, the offsets); no host synchronisation; n_meas == 0 launches nothing.  RG_ERR_ARG,
+ * launching nothing: a negative size, a NULL array with n_meas > 0, a workspace smaller than
+ * rg_train_offsets_workspace_size(n_tracks) or not 8-byte aligned. */
+size_t rg_train_offsets_workspace_size(int n_tracks);
+int rg_train_offsets(const int* track_key, int n_tracks, const float* px, const float* py,
+                     int n_meas, float* offset_x, float* offset_y, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------ proposal branch */
 
 /* Predicted cluster centres (gnn_detector.py:164-167): unnormalize_gt_offsets
