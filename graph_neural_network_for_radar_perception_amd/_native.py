@@ -208,6 +208,13 @@ _SIGNATURES = {
     'rg_conv_layer_x3_split_for': (_I, [ctypes.POINTER(rg_layer), ctypes.POINTER(rg_layer),
                                         ctypes.POINTER(rg_layer), _I, _P, _I, _P, _I, _P, _P, _P,
                                         _P, _I, _P, _I, _P, _P, _P, _S, _P]),
+    # classifier conv layer over complete object graphs (cls_conv_x3.hip)
+    'rg_cls_object_table_bytes': (_S, [_I, _I]),
+    'rg_cls_object_table_workspace_size': (_S, [_I]),
+    'rg_cls_object_table': (_I, [_P, _I, _I, _L, _P, _P, _S, _P]),
+    'rg_cls_conv_layer_x3_workspace_size': (_S, [_I, _I]),
+    'rg_cls_conv_layer_x3': (_I, [ctypes.POINTER(rg_layer), _I, _P, _I, _P, _I, _I, _P, _I, _P,
+                                  _S, _P]),
     'rg_conv_layer_workspace_size': (_S, []),
     'rg_conv_layer_fused': (_I, [ctypes.POINTER(rg_layer), ctypes.POINTER(rg_layer), _I, _P, _I,
                                  _P, _I, _P, _P, _P, _I, _P, _I, _P, _P]),

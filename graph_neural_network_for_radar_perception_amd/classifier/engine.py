@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from .. import _native as nat
-from ..engine import (ChainPlan, ConvPlan, DeviceGraph, _require_device, cached_plan,
-                      segment_reduce, specs_from_modules)
+from ..engine import (ChainPlan, ConvPlan, DeviceGraph, LayerSpec, PackedImages, _require_device,
+                      cached_plan, segment_reduce, specs_from_modules)
 
 def _dt(dtype: str):
     return torch.bfloat16 if dtype == 'bf16' else torch.float32
@@ -93,6 +93,119 @@ def object_row_ranges(object_size: torch.Tensor, sample_obj_ptr=None, sample_nod
                                        begin.data_ptr(), end.data_ptr(), ws.data_ptr(), ws.numel(),
                                        nat.stream_ptr(dev)), 'rg_object_row_ranges')
     return begin[:n_obj], end[:n_obj]
+
+
+# --------------------------------------------------------------------------- fused layer
+def object_table(object_size: torch.Tensor, n_nodes: int, n_edges: int) -> torch.Tensor:
+    """The per-batch table of rg_cls_conv_layer_x3 (rg_cls_object_table): seg_ptr, every node's
+    object begin and size, and the edge launch's wave table -- O(n_nodes + n_obj) int32, built
+    from object sizes int64 [n_obj] on the device; shared by the batch's layers."""
+    _require_device(object_size, 'object_size')
+    lib = nat.lib()
+    dev = object_size.device
+    osz = object_size.to(torch.int64).contiguous()
+    n_obj = int(osz.numel())
+    table = torch.empty(lib.rg_cls_object_table_bytes(n_nodes, n_obj) // 4, dtype=torch.int32,
+                        device=dev)
+    ws = torch.empty(lib.rg_cls_object_table_workspace_size(n_obj), dtype=torch.uint8, device=dev)
+    nat.check(lib.rg_cls_object_table(osz.data_ptr(), n_obj, int(n_nodes), int(n_edges),
+                                      table.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      nat.stream_ptr(dev)), 'rg_cls_object_table')
+    return table
+
+
+class ClsFusedPlan:
+    """The image set of one conv block for rg_cls_conv_layer_x3 (fp32, the exact three-term
+    bf16 scheme): [0] the per-node projection [W_0's x_i columns; its x_j columns] (+ [b_0; 0]),
+    [1] msg1, [2] upd.  The specs are derived from the block's msg and upd parameters, which the
+    set's validity follows (PackedImages: refresh() / invalidate()).  fused is None for a block
+    the kernel is not compiled for; fused_ok records the kernel's own answer."""
+
+    C = 128
+    FMTS = (nat.RG_PACK_FAST_IN | nat.RG_PACK_X3, nat.RG_PACK_FAST_CHAIN | nat.RG_PACK_X3,
+            nat.RG_PACK_FAST_IN | nat.RG_PACK_X3)
+
+    def __init__(self, blk, device):
+        self.aggr = blk.aggr
+        self.device = torch.device(device)
+        self.msg_specs = specs_from_modules(list(blk.msg))
+        self.upd_specs = specs_from_modules(list(blk.upd))
+        self.has_res = blk.residual_connection is not None
+        self.fused_ok = None
+        self.fused = None
+        self.images = None
+        self._ws = {}
+        self._pack()
+
+    def _specs(self):
+        if self.has_res or self.aggr not in nat.REDUCE:
+            return None
+        if len(self.msg_specs) != 2 or len(self.upd_specs) != 1:
+            return None
+        m0, m1 = self.msg_specs
+        u = self.upd_specs[0]
+        C = self.C
+        # compiled for the yml block only: C = 128, hidden 128, no norm, LeakyReLU
+        if not (tuple(m0.weight.shape) == (C, 2 * C) and tuple(m1.weight.shape) == (C, C)
+                and tuple(u.weight.shape) == (C, 2 * C)):
+            return None
+        if any(sp.mu is not None or sp.act != 'leakyrelu' for sp in (m0, m1, u)):
+            return None
+        W = m0.weight.detach().to(torch.float32)
+        b = (m0.bias.detach().to(torch.float32) if m0.bias is not None
+             else torch.zeros(C, dtype=torch.float32, device=W.device))
+        # cat(x_i, x_j): columns [:C] meet the destination's row (P, with b_0), [C:] the source's
+        pq = LayerSpec(torch.cat((W[:, :C], W[:, C:]), 0).contiguous(),
+                       torch.cat((b, torch.zeros_like(b)), 0).contiguous(), None, None, m0.act)
+        return [pq, m1, u]
+
+    def _pack(self):
+        self.fused = None
+        specs = self._specs()
+        if specs is None:
+            return
+        if self.images is None:
+            self.images = PackedImages(specs, self.device, self.msg_specs + self.upd_specs)
+        self.images.specs = specs
+        self.images.get(self.FMTS)
+        self.fused = True
+
+    def refresh(self):
+        if self.fused and self.images.refresh():
+            self._pack()
+
+    def invalidate(self):
+        if self.images is not None:
+            self.images.invalidate()
+
+    def ready(self, x) -> bool:
+        return bool(self.fused) and self.fused_ok is not False and x.dtype == torch.float32
+
+    def run(self, x, table, n_obj: int, x_out) -> bool:
+        """One rg_cls_conv_layer_x3 call; False when the kernel refuses the layer (the caller
+        then runs the unfused chains)."""
+        lib = nat.lib()
+        st = nat.stream_ptr(x.device)
+        n = int(x.shape[0])
+        need = lib.rg_cls_conv_layer_x3_workspace_size(n, n_obj)
+        ws = self._ws.get(st)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[st] = torch.empty(max(int(need), 1), dtype=torch.uint8, device=self.device)
+        rc = lib.rg_cls_conv_layer_x3(self.images.get(self.FMTS)[0][0], nat.REDUCE[self.aggr],
+                                      x.data_ptr(), x.stride(0), table.data_ptr(), n, n_obj,
+                                      x_out.data_ptr(), x_out.stride(0), ws.data_ptr(), ws.numel(),
+                                      st)
+        if rc == nat.RG_ERR_UNSUPPORTED:
+            self.fused_ok = False
+            return False
+        nat.check(rc, 'rg_cls_conv_layer_x3')
+        self.fused_ok = True
+        return True
+
+
+def fused_plan(blk, dev) -> ClsFusedPlan:
+    """The block's fused-layer plan (fp32)."""
+    return cached_plan(blk, ('cls_fused', 'fp32'), lambda: ClsFusedPlan(blk, dev))
 
 
 # --------------------------------------------------------------------------- forward
@@ -183,6 +296,53 @@ def forward_graph(model, node_features: torch.Tensor, g: DeviceGraph, begin: tor
     enc(N, x, xin, xin.shape[1])
     _mark(events, 'node_encoder:end', dev)
     for blk in model.pass_messages.conv_blk:
+        x = run_conv_block_nodes(blk, x, None, dtype, g, events)
+    _mark(events, 'pool_head:start', dev)
+    out = pool_and_classify(model.predict_node, x, begin, end, dtype)
+    _mark(events, 'pool_head:end', dev)
+    return out
+
+
+def forward_objects(model, node_features: torch.Tensor, object_size: torch.Tensor,
+                    begin: torch.Tensor, end: torch.Tensor, dtype: str = 'fp32', n_nodes=None,
+                    n_edges=None, events=None) -> torch.Tensor:
+    """forward_graph straight from the object sizes int64 [n_obj] (the batch's graph is the
+    union of complete graphs over consecutive rows): every conv block the fused kernel takes
+    (fp32, the yml widths, no residual projection) runs rg_cls_conv_layer_x3 over the table of
+    rg_cls_object_table, built once per call -- no edge list, no message buffer.  Any other block
+    runs run_conv_block_nodes over object_graph's CSR, built lazily and once.  n_nodes / n_edges:
+    host integers (sum n, sum n (n - 1)); read back from object_size when not given."""
+    _require_device(node_features, 'node_features')
+    dev = node_features.device
+    osz = object_size.to(dev).to(torch.int64).contiguous()
+    n_obj = int(osz.numel())
+    if n_nodes is None or n_edges is None:
+        hs = osz.cpu().numpy()
+        n_nodes, n_edges = int(hs.sum()), int((hs * (hs - 1)).sum())
+    N = int(n_nodes)
+    enc = _chain_plan(list(model.encode_node_feat.encoder), dtype, dev)
+    x = torch.empty((N, enc.out_dim), dtype=_dt(dtype), device=dev)
+    xin = node_features.to(torch.float32).contiguous()
+    _mark(events, 'node_encoder:start', dev)
+    enc(N, x, xin, xin.shape[1])
+    _mark(events, 'node_encoder:end', dev)
+    table = g = None
+    for blk in model.pass_messages.conv_blk:
+        fp = fused_plan(blk, dev) if dtype == 'fp32' and N > 0 else None
+        if fp is not None and fp.ready(x):
+            if table is None:
+                _mark(events, 'object_table:start', dev)
+                table = object_table(osz, N, int(n_edges))
+                _mark(events, 'object_table:end', dev)
+            out = torch.empty((N, fp.C), dtype=torch.float32, device=dev)
+            _mark(events, 'cls_conv_layer:start', dev)
+            ok = fp.run(x, table, n_obj, out)
+            _mark(events, 'cls_conv_layer:end', dev)
+            if ok:
+                x = out
+                continue
+        if g is None:
+            g = object_graph(osz, N, int(n_edges))
         x = run_conv_block_nodes(blk, x, None, dtype, g, events)
     _mark(events, 'pool_head:start', dev)
     out = pool_and_classify(model.predict_node, x, begin, end, dtype)

@@ -254,9 +254,15 @@ class ClassifierInputs:
         pooling ranges, built from the object sizes on the device (no edge list)."""
         from .classifier import engine as ce
         g = ce.object_graph(self.object_num_meas, self.n_rows, self.n_edges)
-        begin, end = ce.object_row_ranges(self.object_num_meas, self.frame_obj_ptr,
-                                          self.frame_row_ptr, self.n_frames)
+        begin, end = self.ranges()
         return g, begin, end
+
+    def ranges(self):
+        """(begin, end): the reference's pooling ranges alone -- with object_num_meas, n_rows
+        and n_edges all that classifier.engine.forward_objects needs (no graph)."""
+        from .classifier import engine as ce
+        return ce.object_row_ranges(self.object_num_meas, self.frame_obj_ptr,
+                                    self.frame_row_ptr, self.n_frames)
 
     def samples(self) -> List[dict]:
         """The reference's per-frame ``training_data`` dicts (datagen_classifier.py:272-280):
@@ -554,9 +560,10 @@ def classify_inputs(classifier_model, inp: ClassifierInputs):
     if inp.n_objects == 0:
         nc = int(model.predict_node.pred_cls.head[1].out_features)
         return torch.zeros((0, nc), dtype=torch.float32, device=inp.object_features.device)
-    g, begin, end = inp.graph()
+    begin, end = inp.ranges()
     with torch.no_grad():
-        return ce.forward_graph(model, inp.object_features, g, begin, end, model.compute_dtype)
+        return ce.forward_objects(model, inp.object_features, inp.object_num_meas, begin, end,
+                                  model.compute_dtype, n_nodes=inp.n_rows, n_edges=inp.n_edges)
 
 
 def classify_proposals(detector, classifier_model, node_features, edge_features, edge_index,

@@ -487,6 +487,42 @@ int rg_conv_layer_x3_split_for(const rg_layer* layers, const rg_layer* next_pq,
                                int ld_out, float* pq_out, const int* table, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* The classifier's conv layer over COMPLETE OBJECT GRAPHS, from the object sizes alone
+ * (cls_conv_x3.hip).  The graph is the block-diagonal union of complete graphs of
+ * compute_edge_index: object o owns the contiguous rows [b_o, b_o + n_o) and the sources of
+ * destination i are those rows without i, ascending.  Nothing of E entries is built or read.
+ *
+ * rg_cls_object_table, once per batch and shared by its layers: from object_size int64[n_obj]
+ * on the device (their sum = n_nodes; the host passes n_nodes and n_edges = sum n (n - 1),
+ * n_edges < 2^31 or RG_ERR_ARG) the int32 table of rg_cls_object_table_bytes(n_nodes, n_obj)
+ * bytes: the destination-major seg_ptr[n_nodes + 1] (degree n_o - 1), every node's object begin
+ * and size, and the edge launch's wave table (pieces of whole destinations with equal edge
+ * counts).  workspace: rg_cls_object_table_workspace_size(n_obj) bytes.  No host
+ * synchronisation; n_nodes == 0 launches nothing. */
+size_t rg_cls_object_table_bytes(int n_nodes, int n_obj);
+size_t rg_cls_object_table_workspace_size(int n_obj);
+int rg_cls_object_table(const int64_t* object_size, int n_obj, int n_nodes, long n_edges,
+                        int* table, void* workspace, size_t workspace_bytes, void* stream);
+/* One residual conv block of the classifier (classifier/blocks.py:28-85),
+ *   x_out[i] = x[i] + leaky(W_u cat(x[i], AGG_{j in object(i), j != i} m_ij) + b_u),
+ *   m_ij = leaky(W_1 leaky(P[i] + Q[j]) + b_1),  P | Q = W_pq x + [b_0; 0],
+ * in the exact three-term bf16 arithmetic of rg_conv_layer_x3 (float32's range: the classifier's
+ * activations are not normalised).  layers[0]: the projection [W_0's x_i columns; its x_j
+ * columns] 128 -> 256 with bias [b_0; 0], RG_PACK_FAST_IN | RG_PACK_X3, act = msg0's activation;
+ * layers[1]: msg1 128 -> 128, RG_PACK_FAST_CHAIN | RG_PACK_X3; layers[2]: upd 256 -> 128 over
+ * cat(x, agg), RG_PACK_FAST_IN | RG_PACK_X3; all un-centred, no norm, RG_ACT_LEAKYRELU.
+ * aggr: RG_REDUCE_SUM, _MEAN (by n_o - 1) or _MAX, summed in ascending source order; a node of
+ * a one-member object aggregates zeros.  Three launches, no atomics: results are
+ * bit-reproducible, and an object's rows do not depend on the other objects of the batch.
+ * workspace: rg_cls_conv_layer_x3_workspace_size(n_nodes, n_obj) bytes (no edge count), need
+ * not be zeroed.  RG_ERR_UNSUPPORTED, launching nothing, for any other shape, activation, norm
+ * or a centred image; RG_ERR_ARG for x == x_out, a short workspace or an RG_LAYER_H2 /
+ * RG_LAYER_F16 image; n_nodes <= 0 is a no-op. */
+size_t rg_cls_conv_layer_x3_workspace_size(int n_nodes, int n_obj);
+int rg_cls_conv_layer_x3(const rg_layer* layers, int aggr, const float* x, int ldx,
+                         const int* table, int n_nodes, int n_obj, float* x_out, int ld_out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* One fused residual_graph_conv_block (gnn_blocks.py:96-113) for the shipped
  * widths (node / edge channels 64, msg MLP 192->128->64, update 128->64, all with
  * channel_normalization), bf16 operands, aggregation add or mean:
