@@ -215,6 +215,13 @@ _SIGNATURES = {
     'rg_cls_conv_layer_x3_workspace_size': (_S, [_I, _I]),
     'rg_cls_conv_layer_x3': (_I, [ctypes.POINTER(rg_layer), _I, _P, _I, _P, _I, _I, _P, _I, _P,
                                   _S, _P]),
+    # its edge phase for training: taped forward, backward (cls_conv_bwd_x3.hip)
+    'rg_cls_conv_aggregate_x3_workspace_size': (_S, [_I]),
+    'rg_cls_conv_aggregate_x3': (_I, [ctypes.POINTER(rg_layer), _I, _P, _I, _P, _I, _P, _P, _P,
+                                      _S, _P]),
+    'rg_cls_conv_backward_x3_workspace_size': (_S, [_I, _I]),
+    'rg_cls_conv_backward_x3': (_I, [ctypes.POINTER(rg_layer), _I, _P, _P, _I, _P, _I, _L, _I, _P,
+                                     _P, _P, _P, _S, _P]),
     'rg_conv_layer_workspace_size': (_S, []),
     'rg_conv_layer_fused': (_I, [ctypes.POINTER(rg_layer), ctypes.POINTER(rg_layer), _I, _P, _I,
                                  _P, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
@@ -250,6 +257,8 @@ _SIGNATURES = {
     'rg_object_focal_loss': (_I, [_P, _I, _P, _I, _I, _P, _P]),
     'rg_object_focal_loss_backward': (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _P]),
     'rg_range_max_backward': (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P]),
+    'rg_range_max_backward_ordered_workspace_size': (_S, [_I, _I]),
+    'rg_range_max_backward_ordered': (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P, _S, _P]),
     'rg_segment_amax_backward': (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     # training (train.hip)
     'rg_ffn_backward_workspace_size': (_S, []),

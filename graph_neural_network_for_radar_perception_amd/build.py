@@ -30,6 +30,7 @@ FLAGS = ['-O3', '-std=c++17', f'--offload-arch={ARCH}', '-fPIC', '-Wall',
 # fp16 register (v_fma_mix_f32); the SLP vectoriser pairs them into a v_pk_fma_f32 behind two
 # unpacking conversions (5 instead of 4 VALU per pair, more registers, spills in two kernels)
 FILE_FLAGS = {'chain_x3.hip': ['-fno-slp-vectorize'],
+              'cls_conv_bwd_x3.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form'],
               'cls_conv_x3.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form'],
               'conv_fused.hip': ['-DRG_NO_PK', '-fno-slp-vectorize'],
               'conv_x3.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form']}

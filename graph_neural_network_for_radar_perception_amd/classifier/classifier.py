@@ -83,3 +83,27 @@ class Model_Training(nn.Module):
         predictions = self.predict(node_features, edge_index, object_size)
         gt = torch.cat([g.to(predictions.device) for g in groundtruths], 0)
         return self.loss(predictions, gt)
+
+    def forward_objects(self, node_features: List[torch.Tensor], object_size: List[torch.Tensor],
+                        groundtruths: List[torch.Tensor]):
+        """forward() without edge_index: each sample's graph is the union of complete graphs over
+        its objects' consecutive rows (compute_edge_index), which the fused conv layer walks
+        straight from the sizes -- no edge list and, in training, no edge-sized tape
+        (classifier/training.py: train_step_loss_objects)."""
+        from . import training
+        if self.pred.compute_dtype != 'fp32' and torch.is_grad_enabled() and \
+                any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError('classifier training runs in float32 (the '
+                                      'reference precision); set compute_dtype = "fp32"')
+        batch = training.prepare_batch_objects(node_features, object_size, groundtruths)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            dev = node_features[0].device
+            eng = getattr(self, '_train_engine', None)
+            if eng is None or eng.device != dev:
+                eng = training.ClassifierTrainEngine(self, dev)
+                object.__setattr__(self, '_train_engine', eng)  # not a submodule
+            return training.train_step_loss_objects(eng, batch)
+        nf, osz, begin, end, labels, n_nodes, n_edges, _ = batch
+        predictions = engine.forward_objects(self.pred, nf, osz, begin, end,
+                                             self.pred.compute_dtype, n_nodes, n_edges)
+        return self.loss(predictions, labels)

@@ -119,11 +119,17 @@ class ClsFusedPlan:
     bf16 scheme): [0] the per-node projection [W_0's x_i columns; its x_j columns] (+ [b_0; 0]),
     [1] msg1, [2] upd.  The specs are derived from the block's msg and upd parameters, which the
     set's validity follows (PackedImages: refresh() / invalidate()).  fused is None for a block
-    the kernel is not compiled for; fused_ok records the kernel's own answer."""
+    the kernel is not compiled for; fused_ok records the kernel's own answer.
+
+    Training (rg_cls_conv_aggregate_x3 / rg_cls_conv_backward_x3) adds two images that follow
+    the same parameters: W_1^T in the b3 chain format -- the packer transposes float32 formats
+    only, so it is a derived spec of a second set (bwd_images) -- and W_pq^T in float32 for
+    dx += [dP | dQ] W_pq, the transposed column block (0, 0, C) of the projection."""
 
     C = 128
     FMTS = (nat.RG_PACK_FAST_IN | nat.RG_PACK_X3, nat.RG_PACK_FAST_CHAIN | nat.RG_PACK_X3,
             nat.RG_PACK_FAST_IN | nat.RG_PACK_X3)
+    BWD_FMTS = (nat.RG_PACK_FAST_CHAIN | nat.RG_PACK_X3, nat.RG_PACK_FAST_CHAIN | nat.RG_PACK_X3)
 
     def __init__(self, blk, device):
         self.aggr = blk.aggr
@@ -134,7 +140,9 @@ class ClsFusedPlan:
         self.fused_ok = None
         self.fused = None
         self.images = None
+        self.bwd_images = None
         self._ws = {}
+        self._dx_fast = True
         self._pack()
 
     def _specs(self):
@@ -168,15 +176,29 @@ class ClsFusedPlan:
             self.images = PackedImages(specs, self.device, self.msg_specs + self.upd_specs)
         self.images.specs = specs
         self.images.get(self.FMTS)
+        if self.bwd_images is not None:
+            self.bwd_images.specs = self._bwd_specs()
         self.fused = True
 
+    def _bwd_specs(self):
+        """[msg1, a bare Linear of W_1^T] of rg_cls_conv_backward_x3."""
+        m1 = self.msg_specs[1]
+        wt = m1.weight.detach().to(torch.float32).t().contiguous()
+        return [m1, LayerSpec(wt, None, None, None, 'none')]
+
     def refresh(self):
-        if self.fused and self.images.refresh():
+        if not self.fused:
+            return
+        stale = self.images.refresh()
+        if self.bwd_images is not None and self.bwd_images.refresh():
+            stale = True
+        if stale:
             self._pack()
 
     def invalidate(self):
-        if self.images is not None:
-            self.images.invalidate()
+        for im in (self.images, self.bwd_images):
+            if im is not None:
+                im.invalidate()
 
     def ready(self, x) -> bool:
         return bool(self.fused) and self.fused_ok is not False and x.dtype == torch.float32
@@ -187,10 +209,7 @@ class ClsFusedPlan:
         lib = nat.lib()
         st = nat.stream_ptr(x.device)
         n = int(x.shape[0])
-        need = lib.rg_cls_conv_layer_x3_workspace_size(n, n_obj)
-        ws = self._ws.get(st)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[st] = torch.empty(max(int(need), 1), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(lib.rg_cls_conv_layer_x3_workspace_size(n, n_obj), st)
         rc = lib.rg_cls_conv_layer_x3(self.images.get(self.FMTS)[0][0], nat.REDUCE[self.aggr],
                                       x.data_ptr(), x.stride(0), table.data_ptr(), n, n_obj,
                                       x_out.data_ptr(), x_out.stride(0), ws.data_ptr(), ws.numel(),
@@ -201,6 +220,79 @@ class ClsFusedPlan:
         nat.check(rc, 'rg_cls_conv_layer_x3')
         self.fused_ok = True
         return True
+
+
+    # ------------------------------------------------------------------ training
+    def _workspace(self, need: int, st) -> torch.Tensor:
+        ws = self._ws.get(st)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[st] = torch.empty(max(int(need), 1), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def aggregate(self, x, table, pq, agg, workspaces=None) -> bool:
+        """The layer's projection and edge launches with their results kept
+        (rg_cls_conv_aggregate_x3): pq [N, 256] = P | Q, agg [N, 128] as the update MLP reads
+        it.  False when the kernel refuses the layer.  workspaces: the caller's scratch owner
+        (training.Workspaces: one buffer for all blocks); None: the plan's own."""
+        lib = nat.lib()
+        st = nat.stream_ptr(x.device)
+        n = int(x.shape[0])
+        need = lib.rg_cls_conv_aggregate_x3_workspace_size(n)
+        ws = workspaces.get('cls_agg', need) if workspaces is not None else self._workspace(need, st)
+        rc = lib.rg_cls_conv_aggregate_x3(self.images.get(self.FMTS)[0][0], nat.REDUCE[self.aggr],
+                                          x.data_ptr(), x.stride(0), table.data_ptr(), n,
+                                          pq.data_ptr(), agg.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          st)
+        if rc == nat.RG_ERR_UNSUPPORTED:
+            self.fused_ok = False
+            return False
+        nat.check(rc, 'rg_cls_conv_aggregate_x3')
+        self.fused_ok = True
+        return True
+
+    def backward_edges(self, pq, d_agg, table, n_edges: int, max_degree: int, d_pq, d_w1, d_b1,
+                       workspaces=None):
+        """rg_cls_conv_backward_x3: d_pq [N, 256] = dP | dQ written, d_w1 / d_b1 accumulated;
+        d_agg a [N, 128] view (row stride a multiple of 4).  workspaces as aggregate()'s: the
+        dm / h tapes and rg_linear_grad's partials are about 160 MiB, shared by the blocks."""
+        lib = nat.lib()
+        st = nat.stream_ptr(pq.device)
+        n = int(pq.shape[0])
+        if self.bwd_images is None:
+            self.bwd_images = PackedImages(self._bwd_specs(), self.device,
+                                           self.msg_specs + self.upd_specs)
+        layers = self.bwd_images.get(self.BWD_FMTS)[0][0]
+        need = lib.rg_cls_conv_backward_x3_workspace_size(n, int(max_degree))
+        ws = workspaces.get('cls_bwd', need) if workspaces is not None else self._workspace(need, st)
+        nat.check(lib.rg_cls_conv_backward_x3(
+            layers, nat.REDUCE[self.aggr], pq.data_ptr(), d_agg.data_ptr(), d_agg.stride(0),
+            table.data_ptr(), n, int(n_edges), int(max_degree), d_pq.data_ptr(), d_w1.data_ptr(),
+            d_b1.data_ptr(), ws.data_ptr(), ws.numel(), st), 'rg_cls_conv_backward_x3')
+
+    def dx_pq(self, d_pq, out):
+        """out += d_pq W_pq ([N, 256] x [256, 128]): the float32 chain kernels on the transposed
+        projection, as TrainChain's dX = dZ W."""
+        lib = nat.lib()
+        st = nat.stream_ptr(d_pq.device)
+        rows = int(d_pq.shape[0])
+        block = (0, 0, self.C)
+        if self._dx_fast:
+            fast = self.images.get((nat.RG_PACK_F32_FAST,), True, block)[0][0]
+            rc = lib.rg_mlp_chain_f32_ex(fast, 1, rows, None, nat.IN_DENSE, d_pq.data_ptr(),
+                                         d_pq.stride(0), d_pq.shape[1], None, 0, 0, None, 0, 0,
+                                         None, None, out.data_ptr(), out.stride(0),
+                                         out.data_ptr(), out.stride(0), st)
+            if rc == 0:
+                return
+            if rc != nat.RG_ERR_UNSUPPORTED:
+                nat.check(rc, 'rg_mlp_chain_f32_ex (dx = [dP | dQ] W_pq)')
+            self._dx_fast = False
+        gen = self.images.get((nat.RG_F32,), True, block)[0][0]
+        nat.check(lib.rg_mlp_chain(
+            nat.RG_F32, gen, 1, rows, None, nat.IN_DENSE, nat.RG_F32, d_pq.data_ptr(),
+            d_pq.stride(0), d_pq.shape[1], None, 0, 0, None, 0, 0, None, None, out.data_ptr(),
+            out.stride(0), nat.RG_F32, out.data_ptr(), out.stride(0), nat.RG_F32, st),
+            'rg_mlp_chain (dx = [dP | dQ] W_pq)')
 
 
 def fused_plan(blk, dev) -> ClsFusedPlan:

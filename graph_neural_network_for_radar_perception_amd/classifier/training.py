@@ -8,13 +8,20 @@ backward:
 * focal loss  -> ``rg_object_focal_loss_backward`` (d logits)
 * stem + head -> ``TrainChain.backward`` (activation backward, ``rg_linear_grad``,
   dX = dZ W on the chain kernel)
-* max-pool over the reference's overlapping row ranges -> ``rg_range_max_backward``
+* max-pool over the reference's overlapping row ranges -> ``rg_range_max_backward_ordered``
 * L conv blocks (message MLP on cat(x_i, x_j), ``aggr`` add / mean / max (torch's amax
   backward: ties share the gradient, ``rg_segment_amax_backward``), update MLP on
   cat(x, agg), identity or Linear + channel_normalization residual) -> the detector's
   conv backward without the edge part (x_i: segment sums over the destination-major
   CSR, x_j: sums over each node's source incidence list)
 * encoder -> weights only (its input is data).
+
+From object sizes (``forward_objects`` / ``train_step_loss_objects``): a conv block the fused
+kernel takes (fp32, the yml widths, no residual projection, ``sum`` or ``mean``) keeps
+``x``, ``P | Q``, ``agg`` and the update chain's tape -- nothing sized by the edge count -- and
+its backward recomputes the messages per tile (``rg_cls_conv_backward_x3``: dP | dQ, dW_1, db_1),
+then runs over N rows: dW_0's column blocks (``rg_linear_grad_ld``) and
+dx += [dP | dQ] W_pq.  Any other block runs the unfused block over ``object_graph``'s CSR.
 
 Gradients land in one flat buffer (one view per parameter), like the detector's
 ``TrainEngine``; the autograd node hands torch a copy per parameter so any optimizer
@@ -35,6 +42,7 @@ from . import engine as ce
 
 class _ClsConv:
     def __init__(self, blk, device, ws):
+        self.blk = blk
         self.aggr = blk.aggr
         if self.aggr not in ('add', 'sum', 'mean', 'max'):
             raise NotImplementedError(f'classifier training with aggregation {self.aggr!r}')
@@ -56,6 +64,7 @@ class ClassifierTrainEngine(TrainEngine):
         pred = model_training.pred
         self.device = torch.device(device)
         self.ws = Workspaces(self.device)
+        self.events = None   # a list: HIP events around the fused path's launches (engine._mark)
         self.enc = TrainChain(list(pred.encode_node_feat.encoder), self.device, self.ws)
         self.convs = [_ClsConv(b, self.device, self.ws) for b in pred.pass_messages.conv_blk]
         self.head = TrainChain(pred.predict_node.chain(), self.device, self.ws)
@@ -79,40 +88,51 @@ class ClassifierTrainEngine(TrainEngine):
                 labels: torch.Tensor):
         """Batched samples: node features f32 [N, 5], object graph g, pooling ranges,
         labels int64 [n_obj] -> (loss f32 [1], tape)."""
-        lib = nat.lib()
-        dev = self.device
-        f32 = dict(dtype=torch.float32, device=dev)
         N, E = g.n_nodes, g.n_edges
         n_obj = int(begin.numel())
         T = {'g': g, 'N': N, 'E': E, 'n_obj': n_obj, 'begin': begin, 'end': end}
-        x = torch.empty((N, self.enc.out_dim), **f32)
+        x = torch.empty((N, self.enc.out_dim), dtype=torch.float32, device=self.device)
         xin = nf.to(torch.float32).contiguous()
         T['enc'] = self.enc.forward(N, x, xin, xin.shape[1])
         xs = [x]
         T['conv'] = []
         for cv in self.convs:
-            C = x.shape[1]
-            ct = {}
-            msg = torch.empty((max(E, 1), cv.msg.out_dim), **f32)
-            ct['msg'] = cv.msg.forward(E, msg, x, C, mode=nat.IN_GATHER3, idx0=g.dst, idx1=g.src)
-            ct['msg_out'] = msg   # max aggregation's backward needs the messages
-            agg = torch.empty((N, cv.msg.out_dim), **f32)
-            if E > 0:
-                segment_reduce(msg, g.seg_ptr, N, cv.aggr, agg)
-            else:
-                agg.zero_()
-            if cv.res is not None:
-                ident = torch.empty((N, cv.upd.out_dim), **f32)
-                ct['res'] = cv.res.forward(N, ident, x, C)
-            else:
-                ident = x
-            xn = torch.empty((N, cv.upd.out_dim), **f32)
-            ct['upd'] = cv.upd.forward(N, xn, x, C, mode=nat.IN_CONCAT2, in1=agg,
-                                       w1=cv.msg.out_dim, residual=ident)
+            ct, x = self._block_forward(cv, x, g)
             T['conv'].append(ct)
-            x = xn
             xs.append(x)
         T['xs'] = xs
+        return self._pool_head_loss(T, x, labels), T
+
+    def _block_forward(self, cv, x, g: DeviceGraph):
+        """One taped unfused conv block over g: (tape, x_out)."""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        N, E = g.n_nodes, g.n_edges
+        C = x.shape[1]
+        ct = {}
+        msg = torch.empty((max(E, 1), cv.msg.out_dim), **f32)
+        ct['msg'] = cv.msg.forward(E, msg, x, C, mode=nat.IN_GATHER3, idx0=g.dst, idx1=g.src)
+        ct['msg_out'] = msg   # max aggregation's backward needs the messages
+        agg = torch.empty((N, cv.msg.out_dim), **f32)
+        if E > 0:
+            segment_reduce(msg, g.seg_ptr, N, cv.aggr, agg)
+        else:
+            agg.zero_()
+        if cv.res is not None:
+            ident = torch.empty((N, cv.upd.out_dim), **f32)
+            ct['res'] = cv.res.forward(N, ident, x, C)
+        else:
+            ident = x
+        xn = torch.empty((N, cv.upd.out_dim), **f32)
+        ct['upd'] = cv.upd.forward(N, xn, x, C, mode=nat.IN_CONCAT2, in1=agg,
+                                   w1=cv.msg.out_dim, residual=ident)
+        return ct, xn
+
+    def _pool_head_loss(self, T: dict, x, labels):
+        """Max-pool over the objects' row ranges, stem + head, focal loss -> loss f32 [1]."""
+        lib = nat.lib()
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        N, n_obj, begin, end = T['N'], T['n_obj'], T['begin'], T['end']
         C = x.shape[1]
         pooled = torch.empty((max(n_obj, 1), C), **f32)
         ws = torch.empty(lib.rg_segment_reduce_ranges_workspace_size(N, C, nat.RG_F32),
@@ -126,7 +146,78 @@ class ClassifierTrainEngine(TrainEngine):
         lab = labels.to(torch.int64).contiguous()
         loss = ce.focal_loss(logits[:n_obj], lab).reshape(1)
         T.update(logits=logits, labels=lab, pooled=pooled)
-        return loss, T
+        return loss
+
+    def forward_objects(self, nf: torch.Tensor, object_size: torch.Tensor, begin: torch.Tensor,
+                        end: torch.Tensor, labels: torch.Tensor, n_nodes=None, n_edges=None,
+                        max_size=None):
+        """forward() straight from the object sizes int64 [n_obj] (the batch's graph is the union
+        of complete graphs over consecutive rows).  A block the fused kernel takes keeps x,
+        P | Q, agg and the update chain's tape; the object table is built once per step.  Any
+        other block (other widths, a residual projection, aggr = 'max', a refusal) runs the taped
+        unfused block over object_graph's CSR, built lazily and once.  n_nodes / n_edges /
+        max_size: host integers (sum n, sum n (n - 1), max n); whichever is not given is read
+        back from object_size (a host synchronisation; max_size bounds the backward's tape rows
+        per chunk, so the true maximum is read rather than n_nodes assumed)."""
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        osz = object_size.to(dev).to(torch.int64).contiguous()
+        n_obj = int(begin.numel())
+        if n_nodes is None or n_edges is None:
+            hs = osz.cpu().numpy()
+            n_nodes, n_edges = int(hs.sum()), int((hs * (hs - 1)).sum())
+            max_size = int(hs.max()) if hs.size else 0
+        elif max_size is None:
+            max_size = int(osz.max()) if osz.numel() else 0
+        N, E = int(n_nodes), int(n_edges)
+        max_degree = max(int(max_size) - 1, 0)
+        T = {'g': None, 'N': N, 'E': E, 'n_obj': n_obj, 'begin': begin, 'end': end,
+             'table': None, 'max_degree': max_degree}
+        x = torch.empty((N, self.enc.out_dim), **f32)
+        xin = nf.to(torch.float32).contiguous()
+        T['enc'] = self.enc.forward(N, x, xin, xin.shape[1])
+        xs = [x]
+        T['conv'] = []
+        for cv in self.convs:
+            ct = self._fused_block_forward(cv, x, T, osz) if N > 0 else None
+            if ct is not None:
+                x = ct['out']
+            else:
+                if T['g'] is None:
+                    T['g'] = ce.object_graph(osz, N, E)
+                ct, x = self._block_forward(cv, x, T['g'])
+            T['conv'].append(ct)
+            xs.append(x)
+        T['xs'] = xs
+        return self._pool_head_loss(T, x, labels), T
+
+    def _fused_block_forward(self, cv, x, T: dict, osz):
+        """One conv block through rg_cls_conv_aggregate_x3 and the taped update chain: its tape
+        {'fused', 'x', 'pq', 'agg', 'upd', 'out'}, or None for a block the fused path does not
+        take.  The object table is built into T on first use."""
+        if cv.aggr == 'max':   # its backward needs the messages
+            return None
+        fp = ce.fused_plan(cv.blk, self.device)
+        if not fp.ready(x):
+            return None
+        f32 = dict(dtype=torch.float32, device=self.device)
+        N, C = int(x.shape[0]), fp.C
+        ev = getattr(self, 'events', None)
+        if T['table'] is None:
+            ce._mark(ev, 'object_table:start', self.device)
+            T['table'] = ce.object_table(osz, N, T['E'])
+            ce._mark(ev, 'object_table:end', self.device)
+        pq = torch.empty((N, 2 * C), **f32)
+        agg = torch.empty((N, C), **f32)
+        ce._mark(ev, 'cls_conv_aggregate:start', self.device)
+        ok = fp.aggregate(x, T['table'], pq, agg, self.ws)
+        ce._mark(ev, 'cls_conv_aggregate:end', self.device)
+        if not ok:
+            return None
+        xn = torch.empty((N, C), **f32)
+        ct = {'fused': fp, 'x': x, 'pq': pq, 'agg': agg, 'out': xn}
+        ct['upd'] = cv.upd.forward(N, xn, x, C, mode=nat.IN_CONCAT2, in1=agg, w1=C, residual=x)
+        return ct
 
     # ------------------------------------------------------------------ backward
     def backward(self, T: dict, g_loss: torch.Tensor, zero_grads: bool = True):
@@ -150,41 +241,97 @@ class ClassifierTrainEngine(TrainEngine):
         d_pooled = torch.empty((max(n_obj, 1), C), **f32)
         self.head.backward(T['head'], d_logits, G, din=d_pooled)
         dx = torch.zeros((N, C), **f32)
-        nat.check(lib.rg_range_max_backward(x.data_ptr(), x.stride(0), C, T['begin'].data_ptr(),
-                                            T['end'].data_ptr(), n_obj, d_pooled.data_ptr(),
-                                            d_pooled.stride(0), dx.data_ptr(), dx.stride(0), st),
-                  'rg_range_max_backward')
-        eptr = self._identity_ptr(E)
-        src_ptr, src_lst = self._incidence('src', g.src, None, E, N)
+        # (in object order, not with atomics: the ranges overlap, and a step is bit-reproducible)
+        ev = getattr(self, 'events', None)
+        ce._mark(ev, 'pool_backward:start', dev)
+        wsb = self.ws.get('rmax', lib.rg_range_max_backward_ordered_workspace_size(n_obj, C))
+        nat.check(lib.rg_range_max_backward_ordered(
+            x.data_ptr(), x.stride(0), C, T['begin'].data_ptr(), T['end'].data_ptr(), n_obj,
+            d_pooled.data_ptr(), d_pooled.stride(0), dx.data_ptr(), dx.stride(0), wsb.data_ptr(),
+            wsb.numel(), st), 'rg_range_max_backward_ordered')
+        ce._mark(ev, 'pool_backward:end', dev)
+        inc = None   # (identity ptr, source incidence) of g: built when a block ran unfused
         for li in range(len(self.convs) - 1, -1, -1):
             cv, ct = self.convs[li], T['conv'][li]
-            Cin = T['xs'][li].shape[1]
-            Cm = cv.msg.out_dim
-            d_updin = torch.empty((N, Cin + Cm), **f32)
-            cv.upd.backward(ct['upd'], dx.clone(), G, din=d_updin)
-            if cv.res is not None:
-                dx_new = torch.empty((N, Cin), **f32)
-                cv.res.backward(ct['res'], dx, G, din=dx_new)
-            else:
-                dx_new = dx
-            self._add_cols(d_updin, 0, Cin, dx_new)
-            if E > 0:
-                d_msg = torch.empty((E, Cm), **f32)
-                if cv.aggr == 'max':
-                    m = ct['msg_out']
-                    nat.check(lib.rg_segment_amax_backward(
-                        m.data_ptr(), m.stride(0), Cm, g.seg_ptr.data_ptr(), N,
-                        d_updin[:, Cin:].data_ptr(), d_updin.stride(0), d_msg.data_ptr(),
-                        d_msg.stride(0), st), 'rg_segment_amax_backward')
-                else:
-                    scale = self._mean_scale(g, N) if cv.aggr == 'mean' else None
-                    self._segsum(d_updin, Cin, Cm, eptr, g.dst, scale, d_msg, accumulate=False)
-                dG = torch.empty((E, cv.msg.in_dim), **f32)
-                cv.msg.backward(ct['msg'], d_msg, G, din=dG)
-                self._segsum(dG, 0, Cin, g.seg_ptr, None, None, dx_new, accumulate=True)
-                self._segsum(dG, Cin, Cin, src_ptr, src_lst, None, dx_new, accumulate=True)
-            dx = dx_new
+            if ct.get('fused') is not None:
+                dx, _ = self._fused_block_backward(cv, ct, T, dx, G)
+                continue
+            if inc is None:
+                inc = self._graph_incidence(g)
+            dx = self._block_backward(cv, ct, g, inc, T['xs'][li].shape[1], dx, G)
         self.enc.backward(T['enc'], dx, G)
+
+    def _graph_incidence(self, g: DeviceGraph):
+        return (self._identity_ptr(g.n_edges),) + self._incidence('src', g.src, None, g.n_edges,
+                                                                  g.n_nodes)
+
+    def _block_backward(self, cv, ct, g: DeviceGraph, inc, Cin: int, dx, G):
+        """Backward of a block taped by _block_forward: dx of the block input."""
+        lib = nat.lib()
+        st = nat.stream_ptr(self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        N, E = g.n_nodes, g.n_edges
+        eptr, src_ptr, src_lst = inc
+        Cm = cv.msg.out_dim
+        d_updin = torch.empty((N, Cin + Cm), **f32)
+        cv.upd.backward(ct['upd'], dx.clone(), G, din=d_updin)
+        if cv.res is not None:
+            dx_new = torch.empty((N, Cin), **f32)
+            cv.res.backward(ct['res'], dx, G, din=dx_new)
+        else:
+            dx_new = dx
+        self._add_cols(d_updin, 0, Cin, dx_new)
+        if E > 0:
+            d_msg = torch.empty((E, Cm), **f32)
+            if cv.aggr == 'max':
+                m = ct['msg_out']
+                nat.check(lib.rg_segment_amax_backward(
+                    m.data_ptr(), m.stride(0), Cm, g.seg_ptr.data_ptr(), N,
+                    d_updin[:, Cin:].data_ptr(), d_updin.stride(0), d_msg.data_ptr(),
+                    d_msg.stride(0), st), 'rg_segment_amax_backward')
+            else:
+                scale = self._mean_scale(g, N) if cv.aggr == 'mean' else None
+                self._segsum(d_updin, Cin, Cm, eptr, g.dst, scale, d_msg, accumulate=False)
+            dG = torch.empty((E, cv.msg.in_dim), **f32)
+            cv.msg.backward(ct['msg'], d_msg, G, din=dG)
+            self._segsum(dG, 0, Cin, g.seg_ptr, None, None, dx_new, accumulate=True)
+            self._segsum(dG, Cin, Cin, src_ptr, src_lst, None, dx_new, accumulate=True)
+        return dx_new
+
+    def _fused_block_backward(self, cv, ct, T, dx, G):
+        """Backward of a block taped by forward_objects' fused path: (dx of the block input,
+        dP | dQ [N, 256])."""
+        lib = nat.lib()
+        st = nat.stream_ptr(self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        fp, x = ct['fused'], ct['x']
+        N, C = int(x.shape[0]), fp.C
+        m0, m1 = cv.msg.specs
+        # update MLP on cat(x, agg) with the identity residual: dx += its x columns
+        d_updin = torch.empty((N, 2 * C), **f32)
+        cv.upd.backward(ct['upd'], dx.clone(), G, din=d_updin)
+        self._add_cols(d_updin, 0, C, dx)
+        # the edge phase: dP | dQ, dW_1, db_1
+        d_pq = torch.empty((N, 2 * C), **f32)
+        db1 = G[id(m1.bias)] if m1.bias is not None else torch.zeros(C, **f32)
+        ev = getattr(self, 'events', None)
+        ce._mark(ev, 'cls_conv_backward:start', self.device)
+        fp.backward_edges(ct['pq'], d_updin[:, C:], T['table'], T['E'], T['max_degree'], d_pq,
+                          G[id(m1.weight)], db1, self.ws)
+        ce._mark(ev, 'cls_conv_backward:end', self.device)
+        # P | Q = W_pq x + [b_0; 0] over N rows: dW_0's x_i and x_j column blocks, db_0, dx
+        dW0 = G[id(m0.weight)]
+        wsz = lib.rg_linear_grad_workspace_size(N, C, C)
+        ws = self.ws.get('lgrad', wsz)
+        for half in (0, 1):
+            db0 = G[id(m0.bias)] if (half == 0 and m0.bias is not None) else None
+            nat.check(lib.rg_linear_grad_ld(
+                d_pq.data_ptr() + 4 * C * half, d_pq.stride(0), N, C, C, nat.IN_DENSE,
+                x.data_ptr(), x.stride(0), C, None, 0, 0, None, 0, 0, None, None,
+                dW0.data_ptr() + 4 * C * half, dW0.stride(0), nat.ptr(db0), ws.data_ptr(),
+                ws.numel(), st), 'rg_linear_grad_ld (dW_0 column block)')
+        fp.dx_pq(d_pq, dx)
+        return dx, d_pq
 
 
 class _ClsTrainStep(torch.autograd.Function):
@@ -231,3 +378,47 @@ def prepare_batch(node_features: List[torch.Tensor], edge_index: List[torch.Tens
 def train_step_loss(engine_: ClassifierTrainEngine, batch) -> torch.Tensor:
     """Scalar classifier loss with the native backward attached."""
     return _ClsTrainStep.apply(engine_, batch, *engine_.params)
+
+
+class _ClsTrainStepObjects(_ClsTrainStep):
+    """_ClsTrainStep over ClassifierTrainEngine.forward_objects."""
+
+    @staticmethod
+    def forward(ctx, engine_, batch, *params):
+        nf, osz, begin, end, labels, n_nodes, n_edges, max_size = batch
+        loss, tape = engine_.forward_objects(nf, osz, begin, end, labels, n_nodes, n_edges,
+                                             max_size)
+        ctx.engine = engine_
+        ctx.tape = tape
+        return loss[0]
+
+
+def prepare_batch_objects(node_features: List[torch.Tensor], object_size: List[torch.Tensor],
+                          groundtruths: List[torch.Tensor]):
+    """The list arguments of Model_Training.forward_objects (forward's without edge_index) as
+    one batch on the device: (node features, object sizes, pooling begin / end, labels, n_nodes,
+    n_edges, max object size) -- the last three host integers from the sizes."""
+    dev = node_features[0].device
+    sizes = [int(t.shape[0]) for t in node_features]
+    bases = np.cumsum([0] + sizes)
+    nf = torch.cat([t.to(torch.float32) for t in node_features], 0)
+    hs = np.concatenate([o.detach().cpu().numpy().astype(np.int64).reshape(-1)
+                         for o in object_size])
+    osz = torch.from_numpy(hs).to(dev)
+    if len(node_features) == 1:
+        sobj = nbase = None
+    else:
+        nobj = np.cumsum([0] + [int(o.numel()) for o in object_size])
+        sobj = torch.tensor(nobj, dtype=torch.int32).to(dev)
+        nbase = torch.tensor(bases[:-1], dtype=torch.int32).to(dev)
+    begin, end = ce.object_row_ranges(osz, sobj, nbase, len(node_features))
+    labels = torch.cat([t.to(dev).to(torch.int64) for t in groundtruths], 0)
+    return (nf, osz, begin, end, labels, int(hs.sum()), int((hs * (hs - 1)).sum()),
+            int(hs.max()) if hs.size else 0)
+
+
+def train_step_loss_objects(engine_: ClassifierTrainEngine, batch) -> torch.Tensor:
+    """train_step_loss from object sizes: batch = (nf, object_size, begin, end, labels, n_nodes,
+    n_edges, max_size) as prepare_batch_objects returns it (an integer may be None: read back from
+    object_size)."""
+    return _ClsTrainStepObjects.apply(engine_, tuple(batch), *engine_.params)

@@ -250,6 +250,62 @@ __global__ __launch_bounds__(256) void range_max_backward_kernel(
   atomicAdd(dx + (size_t)arg * lddx + c, d_pooled[(size_t)o * ldp + c]);
 }
 
+// The same without atomics, in two launches: arg[o][c] = the first row of [begin[o], end[o])
+// holding the maximum (-1: an empty range), one thread per (object, channel) ...
+__global__ __launch_bounds__(256) void range_argmax_kernel(
+    const float* __restrict__ x, int ldx, int C, const int* __restrict__ begin,
+    const int* __restrict__ end, int n_obj, int* __restrict__ arg_out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)n_obj * C) return;
+  const int o = (int)(i / C), c = (int)(i % C);
+  const int b = begin[o], e = end[o];
+  int arg = -1;
+  if (b < e) {
+    arg = b;
+    float best = x[(size_t)b * ldx + c];
+    for (int r = b + 1; r < e; ++r) {
+      const float v = x[(size_t)r * ldx + c];
+      if (v > best || (v != v && best == best)) { best = v; arg = r; }  // NaN wins, as torch.max
+    }
+  }
+  arg_out[i] = arg;
+}
+// ... then one thread per channel, which owns that column of dx, adds the objects' gradients in
+// object order: bit-reproducible.  Consecutive objects mostly share their row (the reference's
+// ranges all start near row 0, so the row of a running maximum serves many of them): their
+// gradients are summed in a register and reach dx when the row changes.
+__global__ __launch_bounds__(64) void range_max_scatter_kernel(
+    const int* __restrict__ arg, int n_obj, int C, const float* __restrict__ d_pooled, int ldp,
+    float* __restrict__ dx, int lddx) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  constexpr int U = 8;  // loads in flight
+  int cur = -1;
+  float acc = 0.f;
+  for (int o0 = 0; o0 < n_obj; o0 += U) {
+    int a[U];
+    float d[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int o = o0 + u;
+      a[u] = o < n_obj ? arg[(size_t)o * C + c] : -1;
+      d[u] = o < n_obj ? d_pooled[(size_t)o * ldp + c] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (a[u] < 0) continue;
+      if (a[u] != cur) {
+        if (cur >= 0) dx[(size_t)cur * lddx + c] += acc;
+        cur = a[u];
+        acc = d[u];
+      } else {
+        acc += d[u];
+      }
+    }
+  }
+  if (cur >= 0) dx[(size_t)cur * lddx + c] += acc;
+}
+
 }  // namespace rg
 
 extern "C" int rg_object_focal_loss_backward(const float* logits, int ld, const int64_t* labels,
@@ -272,6 +328,32 @@ extern "C" int rg_range_max_backward(const float* x, int ldx, int C, const int* 
   const long tot = (long)n_obj * C;
   range_max_backward_kernel<<<(tot + 255) / 256, 256, 0, (hipStream_t)stream>>>(
       x, ldx, C, begin, end, n_obj, d_pooled, ldp, dx, lddx);
+  RG_LAUNCH_CHECK();
+  return RG_OK;
+}
+
+extern "C" size_t rg_range_max_backward_ordered_workspace_size(int n_obj, int C) {
+  const size_t n = n_obj > 0 ? n_obj : 0, c = C > 0 ? C : 0;
+  return (n * c * sizeof(int) + 255) / 256 * 256;
+}
+
+extern "C" int rg_range_max_backward_ordered(const float* x, int ldx, int C, const int* begin,
+                                             const int* end, int n_obj, const float* d_pooled,
+                                             int ldp, float* dx, int lddx, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  RG_REQUIRE(n_obj >= 0 && C > 0, RG_ERR_ARG, "rg_range_max_backward_ordered: n_obj=%d C=%d", n_obj,
+             C);
+  RG_REQUIRE(workspace_bytes >= rg_range_max_backward_ordered_workspace_size(n_obj, C) &&
+                 (workspace || n_obj == 0),
+             RG_ERR_ARG, "rg_range_max_backward_ordered: workspace too small");
+  if (n_obj == 0) return RG_OK;
+  const long tot = (long)n_obj * C;
+  int* arg = (int*)workspace;
+  range_argmax_kernel<<<(tot + 255) / 256, 256, 0, (hipStream_t)stream>>>(x, ldx, C, begin, end,
+                                                                          n_obj, arg);
+  RG_LAUNCH_CHECK();
+  range_max_scatter_kernel<<<(C + 63) / 64, 64, 0, (hipStream_t)stream>>>(arg, n_obj, C, d_pooled,
+                                                                          ldp, dx, lddx);
   RG_LAUNCH_CHECK();
   return RG_OK;
 }

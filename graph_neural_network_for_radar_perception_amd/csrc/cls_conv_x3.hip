@@ -32,6 +32,7 @@
 #ifndef RG_X3_SPLIT
 #define RG_X3_SPLIT 4  // builtin conversions in the splits, as conv_x3.hip
 #endif
+#include "cls_conv_common.h"
 #include "scan.h"
 #include "x3_common.h"
 
@@ -40,15 +41,6 @@ namespace clsx3 {
 
 using namespace ::rg::x3;
 
-static constexpr int C = 128;     // node / message / output channels
-static constexpr int HID = 128;   // msg hidden width
-static constexpr int PQW = 2 * HID;
-static constexpr int FT = 512;    // edge launch: 8 waves, two per SIMD
-static constexpr int NW = FT / 64;
-static constexpr int GMAX = 256;  // workgroups of the edge launch at most (one per CU)
-static constexpr int TR = 8;      // message rows per LDS transposition pass
-static constexpr int TS = C + 4;  // LDS row stride (floats) of the message tile
-static constexpr int T_BYTES = TR * TS * 4;
 static constexpr int NFT = 256;   // node and projection launches: 4 waves, one per SIMD
 
 enum { RED_SUM = RG_REDUCE_SUM, RED_MEAN = RG_REDUCE_MEAN, RED_MAX = RG_REDUCE_MAX };
@@ -61,29 +53,7 @@ struct Lay {
 };
 
 // ------------------------------------------------------------------ the object table
-// int32 [seg_ptr N + 1 | begin N | size N | wave table W + 1], each part padded to 16 bytes
-__host__ __device__ inline size_t al4(size_t n) { return (n + 3) & ~(size_t)3; }
-static int edge_groups(int n_nodes) {
-  const int g = (n_nodes + 63) / 64;
-  return g < 1 ? 1 : g > GMAX ? GMAX : g;
-}
-struct Tab {
-  int *seg, *beg, *siz, *wtab;
-};
-static Tab tab_of(int* t, int n_nodes) {
-  const size_t n = n_nodes > 0 ? n_nodes : 0;
-  Tab r;
-  r.seg = t;
-  r.beg = r.seg + al4(n + 1);
-  r.siz = r.beg + al4(n);
-  r.wtab = r.siz + al4(n);
-  return r;
-}
-static size_t tab_ints(int n_nodes) {
-  const size_t n = n_nodes > 0 ? n_nodes : 0;
-  return al4(n + 1) + 2 * al4(n) + al4((size_t)GMAX * NW + 1);
-}
-
+// (layout: cls_conv_common.h)
 __global__ void sizes_kernel(const int64_t* __restrict__ object_size, int n_obj,
                              int* __restrict__ sz, int* __restrict__ pairs) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -407,9 +377,11 @@ __global__ __launch_bounds__(NFT) void cls_node_kernel(const float* x, int ldx,
   }
 }
 
+// the projection and the edge launch: P | Q to pq [N][256], the raw aggregate (a sum or a
+// maximum; rows of nodes without edges unwritten) to agg [N + 1][128]
 template <typename P, int RED>
-static int launch_layer(const rg_layer* layers, const float* x, int ldx, const Tab& tb, int n_nodes,
-                        float* x_out, int ld_out, float* pq, float* agg, hipStream_t st) {
+static int launch_edge_phase(const rg_layer* layers, const float* x, int ldx, const Tab& tb,
+                             int n_nodes, float* pq, float* agg, hipStream_t st) {
   const int tiles = (n_nodes + 31) / 32;
   const int nblk = (tiles + NFT / 64 - 1) / (NFT / 64) < 1024 ? (tiles + NFT / 64 - 1) / (NFT / 64) : 1024;
   cls_proj_kernel<P><<<nblk, NFT, 0, st>>>(x, ldx, n_nodes, (const char*)layers[0].w_packed, pq);
@@ -427,10 +399,39 @@ static int launch_layer(const rg_layer* layers, const float* x, int ldx, const T
   RG_ENSURE_LDS(edge, Lay<P>::LDS);
   edge<<<edge_groups(n_nodes), FT, Lay<P>::LDS, st>>>(a);
   RG_LAUNCH_CHECK();
+  return RG_OK;
+}
+
+template <typename P, int RED>
+static int launch_layer(const rg_layer* layers, const float* x, int ldx, const Tab& tb, int n_nodes,
+                        float* x_out, int ld_out, float* pq, float* agg, hipStream_t st) {
+  const int rc = launch_edge_phase<P, RED>(layers, x, ldx, tb, n_nodes, pq, agg, st);
+  if (rc != RG_OK) return rc;
+  const int tiles = (n_nodes + 31) / 32;
+  const int nblk = (tiles + NFT / 64 - 1) / (NFT / 64) < 1024 ? (tiles + NFT / 64 - 1) / (NFT / 64) : 1024;
   cls_node_kernel<P, RED><<<nblk, NFT, 0, st>>>(x, ldx, agg, tb.siz, n_nodes,
                                                 (const char*)layers[2].w_packed, x_out, ld_out);
   RG_LAUNCH_CHECK();
   return RG_OK;
+}
+
+// The aggregate as the update MLP reads it (cls_node_kernel's agg_rows, written out for the
+// training tape): `mean` divided by n_o - 1, a one-member object's row zero.  One thread per
+// four features.
+template <int RED>
+__global__ void cls_agg_finish_kernel(const float* __restrict__ raw, const int* __restrict__ siz,
+                                      int n_nodes, float* __restrict__ agg) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)n_nodes * (C / 4)) return;
+  const int node = (int)(t / (C / 4));
+  const int deg = siz[node] - 1;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (deg > 0) v = ((const f32x4*)raw)[t];
+  if (RED == RED_MEAN && deg > 0) {
+    const float sc = (float)deg;
+    v = (f32x4){div_rn(v.x, sc), div_rn(v.y, sc), div_rn(v.z, sc), div_rn(v.w, sc)};
+  }
+  ((f32x4*)agg)[t] = v;
 }
 
 }  // namespace clsx3
@@ -533,4 +534,50 @@ extern "C" int rg_cls_conv_layer_x3(const rg_layer* layers, int aggr, const floa
   if (aggr == RG_REDUCE_MEAN)
     return launch_layer<B3, RED_MEAN>(layers, x, ldx, tb, n_nodes, x_out, ld_out, pqr, agg, st);
   return launch_layer<B3, RED_SUM>(layers, x, ldx, tb, n_nodes, x_out, ld_out, pqr, agg, st);
+}
+
+extern "C" size_t rg_cls_conv_aggregate_x3_workspace_size(int n_nodes) {
+  const size_t n = n_nodes > 0 ? n_nodes : 0;
+  return align256_t((n + 1) * C * sizeof(float));  // the edge launch's raw rows [N + 1][128]
+}
+
+extern "C" int rg_cls_conv_aggregate_x3(const rg_layer* layers, int aggr, const float* x, int ldx,
+                                        const int* table, int n_nodes, float* pq, float* agg,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  RG_REQUIRE(layers, RG_ERR_ARG, "rg_cls_conv_aggregate_x3: layers is NULL");
+  const rg_layer& lp = layers[0];
+  const rg_layer& m1 = layers[1];
+  RG_REQUIRE(lp.in_dim == C && lp.out_dim == PQW && m1.in_dim == HID && m1.out_dim == C,
+             RG_ERR_UNSUPPORTED, "rg_cls_conv_aggregate_x3: compiled for 128 -> 256 (P | Q), 128 -> 128");
+  RG_REQUIRE(!lp.norm_mu && !m1.norm_mu && lp.act == ACT_LEAKY && m1.act == ACT_LEAKY,
+             RG_ERR_UNSUPPORTED, "rg_cls_conv_aggregate_x3: un-normalised LeakyReLU layers only");
+  RG_REQUIRE(aggr == RG_REDUCE_SUM || aggr == RG_REDUCE_MEAN, RG_ERR_UNSUPPORTED,
+             "rg_cls_conv_aggregate_x3: aggregation %d (sum and mean have a fused backward)", aggr);
+  RG_REQUIRE(!((lp.flags | m1.flags) & RG_LAYER_CENTERED), RG_ERR_UNSUPPORTED,
+             "rg_cls_conv_aggregate_x3: images are packed un-centred");
+  RG_REQUIRE(ldx % 4 == 0 && ldx >= C, RG_ERR_UNSUPPORTED,
+             "rg_cls_conv_aggregate_x3: the row stride must be a multiple of 4, at least 128");
+  RG_REQUIRE(!((lp.flags | m1.flags) & (RG_LAYER_H2 | RG_LAYER_F16)), RG_ERR_ARG,
+             "rg_cls_conv_aggregate_x3: RG_PACK_X3 images only (the classifier's activations "
+             "leave the h2 domain)");
+  RG_REQUIRE((const void*)x != (const void*)pq && (const void*)x != (const void*)agg &&
+                 pq != agg && (void*)pq != workspace && (void*)agg != workspace,
+             RG_ERR_ARG, "rg_cls_conv_aggregate_x3: x, pq, agg and the workspace must not alias");
+  RG_REQUIRE(workspace_bytes >= rg_cls_conv_aggregate_x3_workspace_size(n_nodes), RG_ERR_ARG,
+             "rg_cls_conv_aggregate_x3: workspace too small");
+  if (n_nodes <= 0) return RG_OK;
+  RG_REQUIRE(x && pq && agg && table && workspace && lp.w_packed && m1.w_packed, RG_ERR_ARG,
+             "rg_cls_conv_aggregate_x3: NULL argument");
+  const Tab tb = tab_of(const_cast<int*>(table), n_nodes);
+  float* raw = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = launch_edge_phase<B3, RED_SUM>(layers, x, ldx, tb, n_nodes, pq, raw, st);
+  if (rc != RG_OK) return rc;
+  const int nblk = ceil_div((long)n_nodes * (C / 4), 256);
+  if (aggr == RG_REDUCE_MEAN)
+    cls_agg_finish_kernel<RED_MEAN><<<nblk, 256, 0, st>>>(raw, tb.siz, n_nodes, agg);
+  else
+    cls_agg_finish_kernel<RED_SUM><<<nblk, 256, 0, st>>>(raw, tb.siz, n_nodes, agg);
+  RG_LAUNCH_CHECK();
+  return RG_OK;
 }

@@ -522,6 +522,44 @@ size_t rg_cls_conv_layer_x3_workspace_size(int n_nodes, int n_obj);
 int rg_cls_conv_layer_x3(const rg_layer* layers, int aggr, const float* x, int ldx,
                          const int* table, int n_nodes, int n_obj, float* x_out, int ld_out,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* The same block for training, edge phase only (the update MLP runs as a taped N-row chain).
+ *
+ * rg_cls_conv_aggregate_x3: the projection and edge launches of rg_cls_conv_layer_x3 with their
+ * results in caller buffers -- pq [n_nodes][256] = P | Q and agg [n_nodes][128] as the update MLP
+ * reads it (`mean` divided by n_o - 1, a one-member object's row zero): the bits the fused layer
+ * aggregates.  layers[0], layers[1] as above.  aggr RG_REDUCE_SUM or _MEAN (RG_REDUCE_MAX:
+ * RG_ERR_UNSUPPORTED -- its backward needs the messages).  workspace:
+ * rg_cls_conv_aggregate_x3_workspace_size(n_nodes) bytes.
+ *
+ * rg_cls_conv_backward_x3 (cls_conv_bwd_x3.hip): from pq and d_agg [n_nodes][128] (row stride
+ * ld_dagg, a multiple of 4) it WRITES d_pq [n_nodes][256] = d P | d Q (rows of one-member
+ * objects zero) and ADDS d W_1 [128][128], d b_1 [128]:
+ *   dm_ij = d_agg[i] leaky'(z1_ij) (mean: times 1 / (n_o - 1)),  dz0_ij = (W_1^T dm_ij) leaky'(z0_ij),
+ *   d P[i] = sum_j dz0_ij,  d Q[j] = sum_i dz0_ij,  d W_1 = sum dm_ij h_ij^T,  d b_1 = sum dm_ij
+ * with z0, h, z1 recomputed per 32-edge tile from pq: nothing sized by the edge count is read,
+ * written or kept.  layers[0]: msg1 as above; layers[1]: a bare Linear of W_1^T (128 -> 128, no
+ * bias), RG_PACK_FAST_CHAIN | RG_PACK_X3.  Each d P / d Q row is summed in ascending partner
+ * order inside one wave: no atomics, bit-reproducible, an object's rows independent of the rest
+ * of the batch.  d W_1 / d b_1: the destination pass runs in chunks of whole destinations of at
+ * most 2^17 + max_degree edges whose dm and h rows go to the workspace and through
+ * rg_linear_grad.  n_edges = sum n (n - 1) < 2^31 (host); max_degree: an upper bound of
+ * n_o - 1 over the objects (n_nodes - 1 always is one, at the price of n_nodes more tape rows per
+ * chunk; with a value below the true maximum d W_1 and d b_1 are undefined -- rows of an earlier
+ * chunk may be added again -- while d_pq stays right and nothing is written out of bounds).
+ * workspace:
+ * rg_cls_conv_backward_x3_workspace_size(n_nodes, max_degree) bytes (no edge count), need not be
+ * zeroed.  Both: RG_ERR_UNSUPPORTED, launching nothing, for any other shape, activation, norm,
+ * aggregation or a centred image; RG_ERR_ARG for an RG_LAYER_H2 / RG_LAYER_F16 image, a short
+ * workspace or aliased buffers; n_nodes <= 0 is a no-op. */
+size_t rg_cls_conv_aggregate_x3_workspace_size(int n_nodes);
+int rg_cls_conv_aggregate_x3(const rg_layer* layers, int aggr, const float* x, int ldx,
+                             const int* table, int n_nodes, float* pq, float* agg,
+                             void* workspace, size_t workspace_bytes, void* stream);
+size_t rg_cls_conv_backward_x3_workspace_size(int n_nodes, int max_degree);
+int rg_cls_conv_backward_x3(const rg_layer* layers, int aggr, const float* pq, const float* d_agg,
+                            int ld_dagg, const int* table, int n_nodes, long n_edges,
+                            int max_degree, float* d_pq, float* d_w1, float* d_b1,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* One fused residual_graph_conv_block (gnn_blocks.py:96-113) for the shipped
  * widths (node / edge channels 64, msg MLP 192->128->64, update 128->64, all with
@@ -715,6 +753,15 @@ int rg_object_focal_loss_backward(const float* logits, int ld, const int64_t* la
 int rg_range_max_backward(const float* x, int ldx, int C, const int* begin, const int* end,
                           int n_obj, const float* d_pooled, int ldp, float* dx, int lddx,
                           void* stream);
+/* The same without atomics: a row's gradients are added in object order by the one thread that
+ * owns its channel -- bit-reproducible, which the atomic form is not once three objects share a
+ * row.  workspace: rg_range_max_backward_ordered_workspace_size(n_obj, C) bytes (the argmax row
+ * of every (object, channel)). */
+size_t rg_range_max_backward_ordered_workspace_size(int n_obj, int C);
+int rg_range_max_backward_ordered(const float* x, int ldx, int C, const int* begin,
+                                  const int* end, int n_obj, const float* d_pooled, int ldp,
+                                  float* dx, int lddx, void* workspace, size_t workspace_bytes,
+                                  void* stream);
 /* Backward of PyG aggr='max' (scatter_reduce amax, include_self=False) over a
  * destination-major CSR whose position p is message row p: d_msg[p][c] = d_agg[s][c] /
  * (number of maxima) for the messages equal to the segment maximum, else 0 (torch's
