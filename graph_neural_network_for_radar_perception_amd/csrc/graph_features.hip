@@ -249,11 +249,19 @@ __global__ void dst_count(const int64_t* __restrict__ ei, long E, int n_nodes,
   atomicAdd(cnt + d, 1);
 }
 
+// Edges with an endpoint out of range were not counted: the dst_ptr[n_nodes] kept edges fill
+// perm[0 .. dst_ptr[n_nodes]), and positions from there to E belong to no segment.  They are
+// written 0 here (no kept edge lands there, and dst_sort stays inside the segments), so that a
+// consumer running over all E positions gathers row 0, not whatever the buffer held.
 __global__ void dst_fill(const int64_t* __restrict__ ei, long E, int n_nodes,
                          const int* __restrict__ dst_ptr, int* __restrict__ cursor,
-                         int* __restrict__ perm) {
+                         int* __restrict__ perm, int* __restrict__ src_sorted) {
   const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= E) return;
+  if (p >= (long)dst_ptr[n_nodes]) {
+    perm[p] = 0;
+    src_sorted[p] = 0;
+  }
   const int64_t s = ei[p], d = ei[E + p];
   if (s < 0 || s >= n_nodes || d < 0 || d >= n_nodes) return;
   const int slot = atomicAdd(cursor + d, 1);
@@ -492,8 +500,10 @@ extern "C" int rg_csr_by_dst(const int64_t* edge_index, long n_edges, int n_node
   if (rc) return rc;
   if (n_edges > 0) {
     dst_fill<<<ceil_div(n_edges, 256), 256, 0, st>>>(edge_index, n_edges, n_nodes, dst_ptr, cursor,
-                                                     perm);
+                                                     perm, src_sorted);
     RG_LAUNCH_CHECK();
+  }
+  if (n_edges > 0 && n_nodes > 0) {
     dst_sort<<<ceil_div(n_nodes, 256), 256, 0, st>>>(edge_index, n_nodes, dst_ptr, perm,
                                                      src_sorted);
     RG_LAUNCH_CHECK();

@@ -138,8 +138,10 @@ extern "C" int rg_cluster_lists(const int* labels, int n_nodes, int* cluster_of,
   cluster_ids<<<ceil_div(n_nodes, 256), 256, 0, st>>>(labels, ws.rank, n_nodes, cluster_of,
                                                       ws.count, ws.iota);
   RG_LAUNCH_CHECK();
-  // cluster_ptr = exclusive scan of the member counts (clusters beyond n_clusters are empty)
-  rc = exclusive_scan(ws.count, n_nodes + 1, cluster_ptr, nullptr, ws.scan_ws, st);
+  // cluster_ptr = exclusive scan of the member counts (clusters beyond n_clusters are empty).
+  // A scan of n inputs writes n + 1 outputs: the n_nodes counts fill cluster_ptr's n_nodes + 1
+  // entries (count[n_nodes] is always 0 and would add one entry past the array).
+  rc = exclusive_scan(ws.count, n_nodes, cluster_ptr, nullptr, ws.scan_ws, st);
   if (rc) return rc;
   // members grouped by cluster, ascending inside each: a stable radix sort of the node
   // indices (already ascending) keyed by cluster id

@@ -1157,7 +1157,10 @@ extern "C" int rg_incidence(const int* a, const int* b, long n_items, int n_node
   int* cnt = (int*)workspace;
   int* cursor = cnt + (n_nodes + 1);
   void* sws = (char*)workspace + ((size_t)2 * (n_nodes + 1) * sizeof(int) + 255) / 256 * 256;
-  if (n_nodes == 0) return RG_OK;
+  if (n_nodes == 0) {  // the empty CSR still has its first offset
+    RG_CHECK_HIP(hipMemsetAsync(ptr, 0, sizeof(int), st));
+    return RG_OK;
+  }
   RG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)n_nodes * sizeof(int), st));
   if (n_items > 0) {
     inc_count<<<ceil_div(n_items, 256), 256, 0, st>>>(a, b, n_items, cnt);

@@ -664,6 +664,8 @@ class DeviceGraph:
     perm     int32[E]    dst-major position -> reference edge position (or None when
                          the dst-major order IS the CSR order of a symmetric graph)
     pair_src/pair_dst int32[U_cap], n_pairs int32[1]: link pairs (i < j) in reference order
+    n_kept_dev int32[1]  from_edge_index only: the edges whose endpoints lie in [0, N), as the
+                         builder counted them (seg_ptr[N]); below E the edge_index is invalid
     """
 
     def __init__(self, n_nodes, n_edges_cap, seg_ptr, dst, src, perm, pair_src, pair_dst,
@@ -681,6 +683,24 @@ class DeviceGraph:
         self.frame_ptr = None      # int32 [B+1] device node offsets of the frames (optional)
         self.n_frames = None
         self._segs = {}
+        self.n_kept_dev = None
+        self._counts_dev = None    # from_edge_index: int32[2] (n_kept, n_pairs), not yet read
+
+    def pair_count(self) -> int:
+        """The number of link pairs, read from the device once and kept in n_pairs.  For a graph
+        of from_edge_index that same read brings the builder's count of in-range edges, and
+        raises IndexError when edges were dropped (the reference's index_select raises for
+        such an edge_index); the check repeats until it passes."""
+        if self._counts_dev is not None:
+            kept, pairs = self._counts_dev.tolist()
+            if kept != self.n_edges:
+                raise IndexError(f'edge_index: {self.n_edges - kept} of {self.n_edges} edges have '
+                                 f'an endpoint outside [0, {self.n_nodes})')
+            self._counts_dev = None
+            self.n_pairs = pairs
+        elif self.n_pairs is None:
+            self.n_pairs = int(self.n_pairs_dev.item())
+        return self.n_pairs
 
     def set_frames(self, frame_ptr: torch.Tensor, n_frames: int):
         """Frame boundaries (node offsets); needed by layer / group normalisation, whose
@@ -781,7 +801,15 @@ class DeviceGraph:
 
     @staticmethod
     def from_edge_index(edge_index: torch.Tensor, n_nodes: int, count_pairs: bool = True):
-        """Reference-order edge_index (int64 [2, E]) -> destination-major CSR."""
+        """Reference-order edge_index (int64 [2, E]) -> destination-major CSR.
+
+        An edge with an endpoint outside [0, n_nodes) makes the edge_index invalid (the
+        reference's index_select raises).  The builder drops such edges and counts the rest in
+        seg_ptr[n_nodes]; with count_pairs that count comes back in the host read of the pair
+        count and IndexError is raised here.  With count_pairs=False nothing is read: the count
+        stays on the graph (n_kept_dev), pair_count() -- the graph's first host read -- raises,
+        and until then the positions past the kept edges hold index 0 in perm / src / dst, so
+        no kernel gathers through unwritten memory."""
         _require_device(edge_index, 'edge_index')
         lib = nat.lib()
         dev = edge_index.device
@@ -789,24 +817,29 @@ class DeviceGraph:
         E = ei.shape[1]
         st = nat.stream_ptr(dev)
         i32 = dict(dtype=torch.int32, device=dev)
-        seg_ptr = torch.empty(n_nodes + 1, **i32)
+        # seg_ptr and the pair count in one allocation: (seg_ptr[n_nodes], n_pairs) is one copy
+        counts = torch.empty(n_nodes + 2, **i32)
+        seg_ptr, npairs = counts[:n_nodes + 1], counts[n_nodes + 1:]
         perm = torch.empty(max(E, 1), **i32)
         src = torch.empty(max(E, 1), **i32)
         ws = torch.empty(lib.rg_csr_by_dst_workspace_size(n_nodes, E), dtype=torch.uint8, device=dev)
         nat.check(lib.rg_csr_by_dst(ei.data_ptr(), E, n_nodes, seg_ptr.data_ptr(), perm.data_ptr(),
                                     src.data_ptr(), ws.data_ptr(), ws.numel(), st), 'rg_csr_by_dst')
-        dst = torch.empty(max(E, 1), **i32)
+        dst = torch.zeros(max(E, 1), **i32)  # rg_csr_rows writes the kept edges' positions only
         nat.check(lib.rg_csr_rows(seg_ptr.data_ptr(), n_nodes, dst.data_ptr(), st), 'rg_csr_rows')
         ps = torch.empty(max(E, 1), **i32)
         pd = torch.empty(max(E, 1), **i32)
-        npairs = torch.zeros(1, **i32)
         ws2 = torch.empty(lib.rg_pairs_from_edge_index_workspace_size(E), dtype=torch.uint8,
                           device=dev)
         nat.check(lib.rg_pairs_from_edge_index(ei.data_ptr(), E, ps.data_ptr(), pd.data_ptr(),
                                                npairs.data_ptr(), ws2.data_ptr(), ws2.numel(), st),
                   'rg_pairs_from_edge_index')
-        U = int(npairs.item()) if count_pairs else None
-        return DeviceGraph(n_nodes, E, seg_ptr, dst, src, perm, ps, pd, npairs, None, E, U)
+        g = DeviceGraph(n_nodes, E, seg_ptr, dst, src, perm, ps, pd, npairs, None, E, None)
+        g.n_kept_dev = counts[n_nodes:n_nodes + 1]
+        g._counts_dev = counts[n_nodes:]
+        if count_pairs:
+            g.pair_count()
+        return g
 
 
 def build_graph(px, py, frame_ptr: torch.Tensor, frame_sizes: List[int], k: int, eps2: float,

@@ -184,20 +184,27 @@ int rg_edge_features_packed(const void* kin, const int64_t* timestamp, const int
  *     (exclusive scan of each row's entries right of the diagonal), n_pairs int32[1];
  *     workspace O(n);
  *   rg_dense_pair_emit: pair_src / pair_dst int32[n_pairs], rows in order, columns
- *     ascending. */
+ *     ascending.
+ * Any nonzero byte of adj is an entry.  At n = 0: row_ptr[0] = 0, *n_pairs = 0, and
+ * rg_dense_pair_emit writes nothing. */
 size_t rg_dense_pair_rows_workspace_size(int n_nodes);
 int rg_dense_pair_rows(const void* adj, int n_nodes, int* row_ptr, int* n_pairs, void* workspace,
                        size_t workspace_bytes, void* stream);
 int rg_dense_pair_emit(const void* adj, int n_nodes, const int* row_ptr, int* pair_src,
                        int* pair_dst, void* stream);
 /* out[r][0..w) = x[idx0[r]] + x[idx1[r]] in float32 (edge_formation's x[i] + x[j],
- * gnn_blocks.py:297) */
+ * gnn_blocks.py:297); rows of x are ldx floats apart, rows of out ld_out (>= w) apart, and
+ * the columns [w, ld_out) of out are left alone. */
 int rg_pair_add_rows_f32(const float* x, int ldx, int w, const int* idx0, const int* idx1,
                          long rows, float* out, int ld_out, void* stream);
 
 /* Undirected link pairs of edge_formation (gnn_blocks.py:295-296):
  * nonzero(triu(adj,1)) row-major == CSR positions with col > row.
- * pair_ptr int32[n_nodes+1]; pair_src/pair_dst int32[capacity]; n_pairs int32[1]. */
+ * pair_ptr int32[n_nodes+1]; pair_src/pair_dst int32[pair_capacity]; n_pairs int32[1].
+ * pair_ptr and *n_pairs are always the true offsets and count.  When *n_pairs exceeds
+ * pair_capacity, a row whose last pair would lie past the capacity is skipped whole
+ * (pair_ptr[row + 1] > pair_capacity): nothing at or past pair_capacity is written, and the
+ * entries of the skipped rows are left alone.  Columns ascend within a row of the CSR. */
 size_t rg_link_pairs_workspace_size(int n_nodes);
 int rg_link_pairs(const int* row_ptr, const int* col, int n_nodes, int* pair_ptr, int* pair_src,
                   int* pair_dst, long pair_capacity, int* n_pairs, void* workspace,
@@ -205,12 +212,17 @@ int rg_link_pairs(const int* row_ptr, const int* col, int n_nodes, int* pair_ptr
 
 /* Link pairs of an arbitrary edge_index (int64[2][E], reference order): the
  * positions with edge_index[0] < edge_index[1], in edge order; equals
- * nonzero(triu(adj,1)) when edge_index = np.where(adj) (graph_features.py:79). */
+ * nonzero(triu(adj,1)) when edge_index = np.where(adj) (graph_features.py:79).
+ * pair_src / pair_dst int32[*n_pairs] (at most n_edges; nothing past *n_pairs is written);
+ * n_pairs int32[1], written at n_edges = 0 too.  The endpoints are only compared, so any
+ * int64 values do; the pairs hold their low 32 bits. */
 size_t rg_pairs_from_edge_index_workspace_size(long n_edges);
 int rg_pairs_from_edge_index(const int64_t* edge_index, long n_edges, int* pair_src, int* pair_dst,
                              int* n_pairs, void* workspace, size_t workspace_bytes, void* stream);
 
-/* out[p] = row of CSR position p (edge_index[0]; destination of a dst-major edge). */
+/* out[p] = row of CSR position p (edge_index[0]; destination of a dst-major edge).
+ * out int32[row_ptr[n_rows]]: positions from row_ptr[n_rows] on belong to no row and are
+ * left alone. */
 int rg_csr_rows(const int* row_ptr, int n_rows, int* out, void* stream);
 
 /* Capacity guard for a graph built by rg_build_graph into a capacity the host has not
@@ -227,7 +239,12 @@ int rg_csr_clamp(int* row_ptr, int n_rows, int* n_edges_dev, long capacity, int*
 
 /* Destination-major CSR of an arbitrary edge_index (int64[2][E], reference order):
  * dst_ptr int32[n_nodes+1]; perm int32[E] (dst-major position -> reference
- * position), ordered by (dst, src, reference position); src_sorted int32[E]. */
+ * position), ordered by (dst, src, reference position); src_sorted int32[E].
+ * An edge with an endpoint outside [0, n_nodes) is not an edge of the graph: it is dropped,
+ * and dst_ptr[n_nodes] -- the number of edges kept -- reports it by falling short of E.  The
+ * kept edges are exact; the E - dst_ptr[n_nodes] positions past them in perm and src_sorted
+ * are written 0.  The caller compares dst_ptr[n_nodes] with E before it trusts the graph
+ * (engine.DeviceGraph.from_edge_index raises IndexError). */
 size_t rg_csr_by_dst_workspace_size(int n_nodes, long n_edges);
 int rg_csr_by_dst(const int64_t* edge_index, long n_edges, int n_nodes, int* dst_ptr, int* perm,
                   int* src_sorted, void* workspace, size_t workspace_bytes, void* stream);
@@ -237,10 +254,11 @@ int rg_csr_by_dst(const int64_t* edge_index, long n_edges, int n_nodes, int* dst
 int rg_dense_adjacency(const float* px, const float* py, const int* row_ptr, const int* col,
                        int n_nodes, uint8_t* adj, float* dist, void* stream);
 
-/* out[r] = (int64) in[r] (edge_index boundary: datagen_gnn.py:123 int64) */
+/* out[r] = (int64) in[r], r < n (edge_index boundary: datagen_gnn.py:123 int64) */
 int rg_i32_to_i64(const int* in, long n, int64_t* out, void* stream);
 
-/* out[r][:] = in[idx[r]][:] for float32 rows of width w */
+/* out[r][:] = in[idx[r]][:] for float32 rows of width w: in and out are dense (rows w
+ * floats apart), out float32[rows][w] */
 int rg_gather_rows_f32(const float* in, const int* idx, long rows, int w, float* out,
                        void* stream);
 
@@ -652,11 +670,13 @@ int rg_frame_norm_backward(const float* z, int ldz, const float* da, int ldda, i
                            const int* seg_ptr, int n_seg, const float* norm_mu,
                            const float* norm_std, int act, float* dz, int lddz, float* d_mu,
                            float* d_std, void* workspace, size_t workspace_bytes, void* stream);
-/* out[t] = table[idx[t]] (device int32; per-frame edge offsets = seg_ptr[frame_ptr]) */
+/* out[t] = table[idx[t]], t < n (device int32; per-frame edge offsets =
+ * seg_ptr[frame_ptr]) */
 int rg_gather_i32(const int* table, const int* idx, int n, int* out, void* stream);
 /* out[t] = first position p in sorted[0..n) with sorted[p] >= queries[t] (n from
  * n_sorted_dev when non-NULL, capped at n_sorted): per-frame offsets of rows sorted by
- * node (link pairs by source, clusters by first member) */
+ * node (link pairs by source, clusters by first member).  out int32[n_queries]; n when every
+ * value is smaller. */
 int rg_lower_bound_i32(const int* sorted, const int* n_sorted_dev, long n_sorted,
                        const int* queries, int n_queries, int* out, void* stream);
 
@@ -720,7 +740,9 @@ int rg_segment_reduce_ranges(const void* src, int src_dtype, int ld_src, long n_
  * no self loops, np.nonzero order.  n_nodes = sum(object_size), n_edges =
  * sum(n (n - 1)).  row_ptr int32[n_nodes+1], col int32[n_edges] (nullable),
  * edge_index int64[2][n_edges] (nullable).  The graph is symmetric: the CSR is also
- * the destination-major view rg_segment_reduce reads. */
+ * the destination-major view rg_segment_reduce reads.  n_nodes may exceed
+ * sum(object_size): the rows past the last object have no edges (row_ptr = n_edges there);
+ * it must not be smaller, and n_edges must be the exact total. */
 size_t rg_object_graph_workspace_size(int n_obj);
 int rg_object_complete_graph(const int64_t* object_size, int n_obj, int n_nodes, long n_edges,
                              int* row_ptr, int* col, int64_t* edge_index, void* workspace,
@@ -731,7 +753,8 @@ int rg_object_complete_graph(const int64_t* object_size, int n_obj, int n_nodes,
  * and its rows start at sample_node_base[s] (both int32; NULL = one sample at row 0).
  * Per sample: begin[0] = 0, begin[c] = object_size[c-1], end = cumsum(object_size),
  * each + the sample's row base -- the reference's startidx, reproduced as written.
- * int32 [n_obj] each; workspace rg_object_graph_workspace_size(n_obj). */
+ * int32 [n_obj] each (nothing is written at n_obj = 0); an empty sample owns no object and
+ * is skipped; workspace rg_object_graph_workspace_size(n_obj). */
 int rg_object_row_ranges(const int64_t* object_size, int n_obj, const int* sample_obj_ptr,
                          const int* sample_node_base, int n_samples, int* begin, int* end,
                          void* workspace, size_t workspace_bytes, void* stream);
@@ -989,7 +1012,9 @@ int rg_cluster_pairs(const float* px, const float* py, const int* pair_src, cons
 /* Cluster ids in the reference's order (ascending lowest node index; frames are
  * concatenated, each numbered from its own first cluster) and the member lists,
  * ascending (gnn_detector.py:180-184): cluster_of int32 [N], cluster_ptr int32 [N+1]
- * (entries past *n_clusters repeat N), cluster_idx int32 [N], *n_clusters device int. */
+ * (entries past *n_clusters repeat N; exactly N + 1 entries are written), cluster_idx
+ * int32 [N], *n_clusters device int.  labels[i] <= i is the lowest node of i's component,
+ * as rg_cluster_radius / rg_cluster_pairs write it. */
 size_t rg_cluster_lists_workspace_size(int n_nodes);
 int rg_cluster_lists(const int* labels, int n_nodes, int* cluster_of, int* cluster_ptr,
                      int* cluster_idx, int* n_clusters, void* workspace, size_t workspace_bytes,
@@ -1182,7 +1207,9 @@ int rg_linear_grad_ld(const float* dz, int lddz, long rows, int out_dim, int in_
                       void* stream);
 
 /* Incidence lists: for node n, every u < n_items with a[u] == n or b[u] == n (b may be
- * NULL), ascending: ptr int32 [n_nodes+1], list int32 [n_items * (b ? 2 : 1)].  The
+ * NULL), ascending: ptr int32 [n_nodes+1], list int32 [n_items * (b ? 2 : 1)].  An item
+ * with a[u] == b[u] is listed twice, so every list entry is one (item, side) of the index
+ * arrays.  At n_nodes = 0 (then n_items = 0) ptr[0] = 0 is still written.  The
  * transpose of an index_select (PyG x_j = x[edge_index[0]], the link pairs' x[i] + x[j]),
  * used to sum its gradient per node in a fixed order. */
 size_t rg_incidence_workspace_size(int n_nodes, long n_items);
