@@ -15,6 +15,7 @@ from typing import List
 import torch
 import torch.nn as nn
 
+from ..engine import cached_plans
 from . import engine
 from .blocks import graph_convolution, graph_feature_encoding, object_class_prediction
 from .loss import Loss
@@ -58,6 +59,45 @@ class Model_Training(nn.Module):
         self.pred = Model_Inference(net_config)
         self.loss = Loss(net_config)
 
+    def train_engine(self, device=None):
+        """The cached float32 tape + backward of this model (classifier/training.py):
+        ClassifierTrainEngine on `device` (default: the parameters')."""
+        from . import training
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        eng = getattr(self, '_train_engine', None)
+        if eng is None or eng.device != dev:
+            eng = training.ClassifierTrainEngine(self, dev)
+            object.__setattr__(self, '_train_engine', eng)  # not a submodule
+        return eng
+
+    def invalidate_plans(self):
+        """Weights were written behind torch's version counters (FusedSGD / FusedAdamW): every
+        packed image made from this model's parameters is stale.  That is every plan
+        engine.cached_plan holds on one of its modules -- the encoder and head ChainPlans, each
+        block's ConvPlan and ClsFusedPlan (forward and backward image sets) -- and the train
+        engine's chains."""
+        for m in self.modules():
+            for p in cached_plans(m):
+                p.invalidate()
+        eng = getattr(self, '_train_engine', None)
+        if eng is not None:
+            eng.invalidate()
+
+    def fused_optimizer(self, optim: str, lr: float, weight_decay: float, momentum: float = 0.9,
+                        milestones=(), gamma: float = 0.1):
+        """set_param_for_training_classifier.py:43-56: 'sgd' (momentum 0.9) or 'adamw', each
+        with the MultiStepLR schedule, as one native launch per step (training.FusedSGD /
+        FusedAdamW); every step ends in invalidate_plans."""
+        if optim not in ('sgd', 'adamw'):
+            raise ValueError(f'optim {optim!r}: the reference configures sgd or adamw')
+        from ..training import FusedAdamW, FusedSGD
+        params = [p for p in self.parameters()]
+        if optim == 'sgd':
+            return FusedSGD(params, lr, momentum, weight_decay, on_update=self.invalidate_plans,
+                            milestones=milestones, gamma=gamma)
+        return FusedAdamW(params, lr, weight_decay, on_update=self.invalidate_plans,
+                          milestones=milestones, gamma=gamma)
+
     def predict(self, node_features: List[torch.Tensor], edge_index: List[torch.Tensor],
                 object_size: List[torch.Tensor]) -> torch.Tensor:
         """Concatenated logits of every sample (one batched native forward)."""
@@ -73,11 +113,7 @@ class Model_Training(nn.Module):
             if self.pred.compute_dtype != 'fp32':
                 raise NotImplementedError('classifier training runs in float32 (the '
                                           'reference precision); set compute_dtype = "fp32"')
-            dev = node_features[0].device
-            eng = getattr(self, '_train_engine', None)
-            if eng is None or eng.device != dev:
-                eng = training.ClassifierTrainEngine(self, dev)
-                object.__setattr__(self, '_train_engine', eng)  # not a submodule
+            eng = self.train_engine(node_features[0].device)
             batch = training.prepare_batch(node_features, edge_index, object_size, groundtruths)
             return training.train_step_loss(eng, batch)
         predictions = self.predict(node_features, edge_index, object_size)
@@ -97,12 +133,8 @@ class Model_Training(nn.Module):
                                       'reference precision); set compute_dtype = "fp32"')
         batch = training.prepare_batch_objects(node_features, object_size, groundtruths)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            dev = node_features[0].device
-            eng = getattr(self, '_train_engine', None)
-            if eng is None or eng.device != dev:
-                eng = training.ClassifierTrainEngine(self, dev)
-                object.__setattr__(self, '_train_engine', eng)  # not a submodule
-            return training.train_step_loss_objects(eng, batch)
+            return training.train_step_loss_objects(self.train_engine(node_features[0].device),
+                                                    batch)
         nf, osz, begin, end, labels, n_nodes, n_edges, _ = batch
         predictions = engine.forward_objects(self.pred, nf, osz, begin, end,
                                              self.pred.compute_dtype, n_nodes, n_edges)

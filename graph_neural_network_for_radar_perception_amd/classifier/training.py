@@ -23,21 +23,30 @@ its backward recomputes the messages per tile (``rg_cls_conv_backward_x3``: dP |
 then runs over N rows: dW_0's column blocks (``rg_linear_grad_ld``) and
 dx += [dP | dQ] W_pq.  Any other block runs the unfused block over ``object_graph``'s CSR.
 
-Gradients land in one flat buffer (one view per parameter), like the detector's
-``TrainEngine``; the autograd node hands torch a copy per parameter so any optimizer
-works.
+Gradients land in one flat buffer (one view per parameter, then one loss slot), like the
+detector's ``TrainEngine``; the autograd node hands torch a copy per parameter so any
+optimizer works.
+
+The loop (``train_model``, training.py:48-135): ``ClassifierTrainer`` is one iteration with
+the fused optimizer (NaN skip and MultiStepLR on the device, one all-reduce bucket),
+``train_classifier_sequence`` feeds it from a ``SequenceStore`` through the detector's
+proposals (``datagen_classifier.py:195-308``) and ``validate_classifier_sequence`` is the
+validation pass.
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
 
 from .. import _native as nat
-from ..engine import DeviceGraph, segment_reduce
+from .. import training as dt
+from ..engine import DeviceGraph, cached_plans, segment_reduce
 from ..training import TrainChain, TrainEngine, Workspaces
 from . import engine as ce
+
+N_LOSS_SLOTS = 1   # the focal loss, in the gradient bucket's tail
 
 
 class _ClsConv:
@@ -68,20 +77,39 @@ class ClassifierTrainEngine(TrainEngine):
         self.enc = TrainChain(list(pred.encode_node_feat.encoder), self.device, self.ws)
         self.convs = [_ClsConv(b, self.device, self.ws) for b in pred.pass_messages.conv_blk]
         self.head = TrainChain(pred.predict_node.chain(), self.device, self.ws)
+        # flat gradient buffer: one view per parameter, then the step's loss -- the ONE bucket of
+        # the data-parallel all-reduce, as TrainEngine's (a NaN loss on any rank skips the step
+        # on every rank)
         self.params = [p for p in model_training.parameters()]
         n = sum(p.numel() for p in self.params)
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.flat_bucket = torch.zeros(n + N_LOSS_SLOTS, dtype=torch.float32, device=self.device)
+        self.flat_grad = self.flat_bucket[:n]
+        self.loss_slots = self.flat_bucket[n:]
         self.grads = {}
         o = 0
         for p in self.params:
             self.grads[id(p)] = self.flat_grad[o:o + p.numel()].view_as(p)
             o += p.numel()
+        # TrainEngine._repack_in_place's memo: the job list it uploaded and its device copy
+        self._repack_key = None
+        self._repack_dev = None
 
     def chains(self):
         out = [self.enc, self.head]
         for cv in self.convs:
             out += cv.chains()
         return out
+
+    def invalidate(self):
+        """Parameters changed behind torch's version counters: the encoder, head and conv
+        chains re-pack as TrainEngine's do (in place by one launch where every held image
+        allows it), and every block's ClsFusedPlan -- whose images are packed from derived
+        copies of the weights, so never in place -- is made stale, both image sets."""
+        super().invalidate()
+        for cv in self.convs:
+            for p in cached_plans(cv.blk):
+                if isinstance(p, ce.ClsFusedPlan):
+                    p.invalidate()
 
     # ------------------------------------------------------------------ forward
     def forward(self, nf: torch.Tensor, g: DeviceGraph, begin: torch.Tensor, end: torch.Tensor,
@@ -422,3 +450,192 @@ def train_step_loss_objects(engine_: ClassifierTrainEngine, batch) -> torch.Tens
     n_edges, max_size) as prepare_batch_objects returns it (an integer may be None: read back from
     object_size)."""
     return _ClsTrainStepObjects.apply(engine_, tuple(batch), *engine_.params)
+
+
+# ------------------------------------------------------------------ trainer and loop
+def classifier_milestones(cfg, starting_iter_num: int = 0):
+    """set_param_for_training_classifier.py:52-56: decay x0.1 at 60 % and 90 % of
+    max_train_iter, shifted by the iteration training resumes from."""
+    return [int(0.6 * cfg.max_train_iter - starting_iter_num),
+            int(0.9 * cfg.max_train_iter - starting_iter_num)]
+
+
+class ClassifierTrainer:
+    """One data-parallel training iteration of the classifier (classifier/training.py:66-81 for
+    one rank's batch): the taped forward from object sizes + focal loss -> backward -> gradient
+    all-reduce -> fused optimizer step, without a host synchronisation.
+
+    train_model's loop rules hold as in RadarGNNTrainer: the loss rides in the gradient bucket's
+    tail, so after the all-reduce every rank holds the sum and the optimizer kernel skips the
+    update everywhere when it is NaN (skip_batch, training.py:40-45, 76-80); the lr follows
+    MultiStepLR at 60 % / 90 % of max_train_iter over the applied steps; cfg.optim picks SGD
+    (momentum 0.9) or AdamW (set_param_for_training_classifier.py:43-56).  Every step ends in
+    Model_Training.invalidate_plans: the optimizer writes the weights behind torch's version
+    counters."""
+
+    def __init__(self, model_training, cfg, world: int = 1, lr: Optional[float] = None,
+                 weight_decay: Optional[float] = None, optim: Optional[str] = None,
+                 momentum: float = 0.9, milestones=None, starting_iter_num: int = 0):
+        if model_training.pred.compute_dtype != 'fp32':
+            raise NotImplementedError('classifier training runs in float32 (the reference '
+                                      'precision); set compute_dtype = "fp32"')
+        self.model = model_training
+        self.cfg = cfg
+        self.world = world
+        lr = cfg.learning_rate if lr is None else lr
+        wd = cfg.weight_decay if weight_decay is None else weight_decay
+        optim = getattr(cfg, 'optim', 'sgd') if optim is None else optim
+        if milestones is None:
+            milestones = classifier_milestones(cfg, starting_iter_num)
+        self.opt = model_training.fused_optimizer(optim, lr, wd, momentum=momentum,
+                                                  milestones=milestones)
+        dt.broadcast_parameters(self.opt.flat, world)
+        model_training.invalidate_plans()
+        self.one = torch.ones(1, dtype=torch.float32, device=self.opt.flat.device)
+
+    @property
+    def engine(self) -> ClassifierTrainEngine:
+        """The model's cached train engine (packed on first use: a HIP device only)."""
+        return self.model.train_engine(self.opt.flat.device)
+
+    def step_objects(self, node_features, object_size, begin, end, labels, n_nodes: int,
+                     n_edges: int, max_size: int) -> torch.Tensor:
+        """One iteration on a batch as prepare_batch_objects / ClassifierInputs give it (the
+        three host integers included, so nothing is read back).  Returns the loss f32 [1] on
+        the device; NaN: the update was skipped and the step not counted."""
+        eng = self.engine
+        loss, tape = eng.forward_objects(node_features, object_size, begin, end, labels,
+                                         int(n_nodes), int(n_edges), int(max_size))
+        eng.backward(tape, self.one)
+        eng.loss_slots.copy_(loss)
+        scale = dt.allreduce_gradients(eng.flat_bucket, self.world)
+        self.opt.step(eng.flat_grad, grad_scale=scale, losses=eng.loss_slots)
+        return loss
+
+    def step_inputs(self, inp):
+        """step_objects from an objects.ClassifierInputs made with node_labels.  A batch
+        without a kept object -- the reference skips a None batch (training.py:64): with
+        ``world == 1`` nothing runs and None is returned.  With ``world > 1`` the rank still
+        joins the all-reduce, with zero gradients and NaN in its loss slot, so every rank
+        skips the step and none waits for a missing peer; None is returned.  ``inp`` None (a
+        batch without a frame, objects.detect_frames) is such a batch."""
+        if inp is None or inp.n_objects == 0:
+            if self.world > 1:
+                eng = self.engine
+                eng.flat_grad.zero_()
+                eng.loss_slots.fill_(float('nan'))
+                scale = dt.allreduce_gradients(eng.flat_bucket, self.world)
+                self.opt.step(eng.flat_grad, grad_scale=scale, losses=eng.loss_slots)
+            return None
+        if inp.object_class is None:
+            raise ValueError('step_inputs needs ClassifierInputs made with node_labels')
+        begin, end = inp.ranges()
+        return self.step_objects(inp.object_features, inp.object_num_meas, begin, end,
+                                 inp.object_class, inp.n_rows, inp.n_edges, inp.max_size)
+
+    def save(self, path):
+        """save_model_weights (training.py:15-17) on rank 0: the reference's state_dict keys."""
+        rank = 0
+        if self.world > 1:
+            import torch.distributed as dist
+            rank = dist.get_rank()
+        if rank == 0:
+            torch.save(self.model.state_dict(), path)
+
+
+def _sequence_inputs(store, detector, cfg, pos, window_size, flags, min_meas, meas_noise_cov,
+                     cache):
+    """One batch of sliding positions to its ClassifierInputs (datagen_classifier.py:195-282 for
+    every window at once): store.windows -> dynamic_frame (flipped by flags) -> frame_batch ->
+    objects.detect_frames -> objects.classifier_inputs with the majority ground-truth labels.
+    None for a batch without a frame."""
+    from .. import frontend, objects
+    ransac = bool(getattr(cfg, 'reject_static_meas_by_ransac', False))
+    win = store.windows(pos, window_size)
+    # (the classifier reads the class labels only: the offsets' mean is left at the default)
+    dd, gd = frontend.dynamic_frame(win, ransac, with_keys=True, flip=flags)
+    fb = frontend.frame_batch(dd, gd)
+    det = objects.detect_frames(detector, fb, cfg, cache=cache)
+    if det is None:
+        return None
+    if meas_noise_cov is None:
+        meas_noise_cov = getattr(cfg, 'meas_noise_cov', det.meas_noise_cov)
+    return objects.classifier_inputs(det.xy, det.rcs, det.cluster_ptr, det.cluster_idx,
+                                     det.frame_ptr, meas_noise_cov, min_meas,
+                                     node_labels=fb.labels['class_labels'],
+                                     num_classes=int(cfg.num_classes))
+
+
+def _batches(indices, batch_windows):
+    if int(batch_windows) < 1:
+        raise ValueError(f'batch_windows={batch_windows} < 1')
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    for k, i0 in enumerate(range(0, int(idx.shape[0]), int(batch_windows))):
+        yield k, idx[i0:i0 + int(batch_windows)]
+
+
+def train_classifier_sequence(store, detector, trainer: ClassifierTrainer, cfg, indices,
+                              window_size: int = 10, batch_windows: int = 64,
+                              augmentation: Optional[bool] = None, min_meas: int = 2,
+                              meas_noise_cov=None, on_step=None) -> torch.Tensor:
+    """Classifier training from a ``sequence.SequenceStore``: the sliding positions ``indices``,
+    in the caller's order, in batches of ``batch_windows``; each batch goes ``store.windows`` ->
+    ``frontend.dynamic_frame`` (with the x-axis flip when ``augmentation``, default
+    cfg.dataset_augmentation; the flags from ``frontend.draw_flips``, numpy's global generator,
+    drawn as ``training.train_sequence`` draws them) -> ``frontend.frame_batch`` -> graph build
+    and the detector's proposal forward under no_grad (``objects.detect_frames``; ``detector``
+    is a Model_Inference with set_param_for_proposal_extraction done) ->
+    ``objects.classifier_inputs`` with the majority ground-truth labels, objects of at least
+    ``min_meas`` members kept (valid_cluster_num_meas_thr) -> ``ClassifierTrainer.step_inputs``.
+    No host work per window; per batch the host waits only where ``select_dynamic``,
+    ``frame_batch``, ``propose_clusters`` and the one read of ``classifier_inputs`` do.
+    ``on_step(step index, positions, flags or None, loss or None, inputs)`` is called after
+    every batch (inputs None for a batch without a frame; step_inputs is called for it too, so
+    a rank of several still joins the step's all-reduce).  Returns the losses f32 [steps] on
+    the device: one entry per batch that had an object (a skipped NaN step keeps its entry)."""
+    from .. import frontend
+    augmentation = bool(cfg.dataset_augmentation if augmentation is None else augmentation)
+    cache: dict = {}
+    losses = []
+    for k, pos in _batches(indices, batch_windows):
+        flags = frontend.draw_flips(int(pos.shape[0])) if augmentation else None
+        inp = _sequence_inputs(store, detector, cfg, pos, window_size, flags, min_meas,
+                               meas_noise_cov, cache)
+        # (a batch without a frame goes to the trainer too: with world > 1 the rank must join
+        # the step's all-reduce, or its peers wait for it)
+        loss = trainer.step_inputs(inp)
+        if loss is not None:
+            losses.append(loss)
+        if on_step is not None:
+            on_step(k, pos, flags, loss, inp)
+    if not losses:
+        return torch.empty(0, dtype=torch.float32, device=trainer.opt.flat.device)
+    return torch.cat(losses)
+
+
+def validate_classifier_sequence(store, detector, model_training, cfg, indices,
+                                 window_size: int = 10, batch_windows: int = 64,
+                                 min_meas: int = 2, meas_noise_cov=None):
+    """The validation loop of train_model (training.py:102-118) over a sequence: the walk of
+    train_classifier_sequence without the flip, under no_grad, through the inference
+    ``forward_objects`` and the focal loss.  Returns (mean of the batch losses that are not
+    NaN, their number) as LossTracker averages them -- (nan, 0) when none counted; the losses
+    are read back once, at the end.  Weights, optimizer state and applied steps are untouched."""
+    from .. import objects
+    cache: dict = {}
+    losses = []
+    with torch.no_grad():
+        for _, pos in _batches(indices, batch_windows):
+            inp = _sequence_inputs(store, detector, cfg, pos, window_size, None, min_meas,
+                                   meas_noise_cov, cache)
+            if inp is None or inp.n_objects == 0:
+                continue
+            logits = objects.classify_inputs(model_training, inp)
+            losses.append(ce.focal_loss(logits, inp.object_class).reshape(1))
+    if not losses:
+        return float('nan'), 0
+    vals = torch.cat(losses).cpu().numpy()
+    vals = vals[~np.isnan(vals)]
+    if vals.size == 0:
+        return float('nan'), 0
+    return float(np.mean(vals, dtype=np.float64)), int(vals.size)

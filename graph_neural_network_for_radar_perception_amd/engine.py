@@ -1475,6 +1475,11 @@ def cached_plan(owner: nn.Module, key, factory):
     return p
 
 
+def cached_plans(owner: nn.Module) -> list:
+    """Every plan cached_plan holds on `owner` (none built: [])."""
+    return list(_block_cache.get(owner, {}).values())
+
+
 def _plan_for(mods, dtype='fp32', device=None) -> ChainPlan:
     return cached_plan(mods[0], (tuple(id(m) for m in mods), dtype),
                        lambda: ChainPlan(specs_from_modules(mods), dtype, device))

@@ -512,31 +512,16 @@ def evaluate_window_batch(win, model, cfg, detection: Optional[DetectionEvaluato
     proposal parameters set; ``cache`` keeps workspaces and buffers between batches.  Returns
     the batch's FrameBatch (``frontend.frame_batch``) and the forward's outputs (None for a
     batch without a frame of more than one node)."""
-    torch = _torch()
-    from . import engine, frontend
-    from .graph_features import build_graph_batch
+    from . import frontend, objects
     if not getattr(model, 'extract_proposals', False):
         raise ValueError('the detector has no proposal branch: set_param_for_proposal_extraction')
     cache = cache if cache is not None else {}
     dd, gd = frontend.dynamic_frame(win, reject_outlier_by_ransac, with_keys=True)
     fb = frontend.frame_batch(dd, gd)
-    if fb.n_frames == 0:
+    det = objects.detect_frames(model, fb, cfg, dtype, cache)
+    if det is None:
         return fb, None
-    gb = build_graph_batch(fb, cfg, ws_cache=cache.setdefault('graph', {}))
-    g = gb.graph
-    other_xy = torch.stack((fb.arrays['meas_px'], fb.arrays['meas_py']), dim=-1)
-
-    def clusters_fn(node_reg, link_cls):
-        return engine.propose_clusters(
-            node_reg, other_xy, fb.frame_ptr, fb.frame_sizes, model.reg_mu, model.reg_sigma,
-            model.clustering_eps, from_links=model.compute_adj_mat_from_links, g=g,
-            link_cls=link_cls, ws_cache=cache.setdefault('proposals', {}))
-
-    with torch.no_grad():
-        out = engine.forward_batched(model.plans(dtype), gb.node_features, gb.edge_features, g,
-                                     None, None, 0, n_pairs_cap=gb.capacity // 2 + 1,
-                                     buffers=cache.setdefault('buffers', {}),
-                                     clusters_fn=clusters_fn)
+    out = det.outputs
     gt_class = fb.labels['class_labels']
     if detection is not None:
         detection.update(out.node_cls, out.obj_cls, out.cluster_ptr, out.cluster_idx, gt_class,

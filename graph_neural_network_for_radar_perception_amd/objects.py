@@ -244,7 +244,7 @@ class ClassifierInputs:
     without labels), object_mu f32 [K', 2], object_sigma f32 [K', 2, 2], object_cluster int32
     [K'] (the source cluster of every kept object), object_frame int32 [K'], frame_obj_ptr /
     frame_row_ptr int32 [F + 1] (each frame's range of objects / feature rows); n_objects,
-    n_rows, n_edges are host integers."""
+    n_rows, n_edges and max_size (the largest kept object; 0 with none) are host integers."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -300,7 +300,8 @@ def classifier_inputs(xy, rcs, cluster_ptr, cluster_idx, frame_ptr=None, meas_no
     >= min_meas (cfg.valid_cluster_num_meas_thr).
 
     ONE host read: the three integers (kept objects, member rows, edges) that size the outputs
-    and the classifier graph -- the only synchronisation of the stage."""
+    and the classifier graph, and the largest kept object (the training tape's bound) -- the
+    only synchronisation of the stage."""
     torch = _torch()
     if int(min_meas) < 0:
         raise ValueError(f'min_meas={min_meas} < 0')
@@ -327,8 +328,14 @@ def classifier_inputs(xy, rcs, cluster_ptr, cluster_idx, frame_ptr=None, meas_no
             idx.data_ptr(), K, sel['cluster_row'].data_ptr(), stats['mu'].data_ptr(),
             stats['eigvec'].data_ptr(), feats.data_ptr(), nat.stream_ptr(dev)),
             'rg_object_features')
-    head = torch.cat([sel['counts'], stats['bad'].to(torch.int64)]).cpu().tolist()  # the one read
-    Kp, Mp, Ep, bad = (int(v) for v in head)
+    # the largest kept object, over the kept entries only (obj['size'] past counts[0] is
+    # uninitialised); it rides the one read
+    kept = torch.arange(K, device=dev) < sel['counts'][0]
+    mx = torch.where(kept, obj['size'], torch.zeros_like(obj['size'])).max().reshape(1) \
+        if K > 0 else torch.zeros(1, dtype=torch.int64, device=dev)
+    head = torch.cat([sel['counts'], stats['bad'].to(torch.int64), mx])
+    head = head.cpu().tolist()                                               # the one read
+    Kp, Mp, Ep, bad, max_size = (int(v) for v in head)
     if bad:
         raise RuntimeError('a member index or a node label outside its range reached the '
                            'object stage')
@@ -338,7 +345,7 @@ def classifier_inputs(xy, rcs, cluster_ptr, cluster_idx, frame_ptr=None, meas_no
         object_sigma=obj['sigma'][:Kp], object_cluster=sel['obj_cluster'][:Kp],
         object_frame=obj['frame'][:Kp], obj_row_ptr=sel['obj_row_ptr'][:Kp + 1],
         frame_obj_ptr=sel['frame_obj_ptr'], frame_row_ptr=sel['frame_row_ptr'], n_objects=Kp,
-        n_rows=Mp, n_edges=Ep, n_frames=F, stats=stats)
+        n_rows=Mp, n_edges=Ep, n_frames=F, max_size=max_size, stats=stats)
 
 
 # ---------------------------------------------------------------- object list
@@ -541,6 +548,48 @@ def detect(detector, node_features: Sequence, edge_features: Sequence, edge_inde
                       frame_sizes=sizes, xy=other_xy, rcs=nf[:, 1],
                       centres=torch.stack((cx, cy), dim=-1),
                       meas_noise_cov=detector.meas_noise_cov)
+
+
+def detect_frames(detector, fb, cfg, dtype: str = 'fp32', cache: Optional[dict] = None):
+    """detect() for a ``frontend.frame_batch`` FrameBatch: the graph build, the detector's
+    proposal forward under no_grad and the Detections of it -- the forward's outputs
+    (``outputs``, engine.ForwardOutputs; link_cls padded to the pair capacity), the GraphBatch
+    (``graph_batch``), frame_ptr, the positions, the rcs column (node_features[:, 1],
+    datagen_classifier.py:256) and the predicted centres.  ``detector`` is a Model_Inference
+    with its proposal parameters set; ``cache`` keeps workspaces and buffers between batches.
+    None for a batch without a frame.  The host waits where propose_clusters does."""
+    torch = _torch()
+    from . import engine
+    from .graph_features import build_graph_batch
+    if not getattr(detector, 'extract_proposals', False):
+        raise ValueError('the detector has no proposal branch: set_param_for_proposal_extraction')
+    if fb.n_frames == 0:
+        return None
+    cache = cache if cache is not None else {}
+    gb = build_graph_batch(fb, cfg, ws_cache=cache.setdefault('graph', {}))
+    g = gb.graph
+    other_xy = torch.stack((fb.arrays['meas_px'], fb.arrays['meas_py']), dim=-1)
+    pcache = cache.setdefault('proposals', {})
+
+    def clusters_fn(node_reg, link_cls):
+        return engine.propose_clusters(
+            node_reg, other_xy, fb.frame_ptr, fb.frame_sizes, detector.reg_mu,
+            detector.reg_sigma, detector.clustering_eps,
+            from_links=detector.compute_adj_mat_from_links, g=g, link_cls=link_cls,
+            ws_cache=pcache)
+
+    with torch.no_grad():
+        out = engine.forward_batched(detector.plans(dtype), gb.node_features, gb.edge_features, g,
+                                     None, None, 0, n_pairs_cap=gb.capacity // 2 + 1,
+                                     buffers=cache.setdefault('buffers', {}),
+                                     clusters_fn=clusters_fn)
+    cx, cy = pcache['proposal_centres']
+    return Detections(node_cls=out.node_cls, node_reg=out.node_reg, link_cls=out.link_cls,
+                      obj_cls=out.obj_cls, cluster_ptr=out.cluster_ptr,
+                      cluster_idx=out.cluster_idx, frame_ptr=fb.frame_ptr,
+                      frame_sizes=fb.frame_sizes, xy=other_xy, rcs=gb.node_features[:, 1],
+                      centres=torch.stack((cx, cy), dim=-1),
+                      meas_noise_cov=detector.meas_noise_cov, outputs=out, graph_batch=gb)
 
 
 def detections_object_list(det: Detections, detect_object_by_segmentation_output: bool = True,
