@@ -137,7 +137,13 @@ class config:
         self.learning_rate = opt['learning_rate']
         self.weight_decay = opt['weight_decay']
         self.include_region_confidence = c['DATASET_INFO']['include_region_confidence']
-        self.clustering_eps = c['FINETUNING']['clustering_eps']
+        # set_config_gnn.py:110-114 (object classification finetuning)
+        ft = c['FINETUNING']
+        self.optim_finetuning = ft['optim']
+        self.max_train_iter_finetuning = ft['max_training_iterations']
+        self.learning_rate_finetuning = ft['learning_rate']
+        self.weight_decay_finetuning = ft['weight_decay']
+        self.clustering_eps = ft['clustering_eps']
         for k, v in (overrides or {}).items():
             setattr(self, k, v)
 

@@ -170,6 +170,19 @@ class Model_Inference(nn.Module):
         if getattr(self, '_train_engine', None) is not None:
             self._train_engine.invalidate()
 
+    def invalidate_head_plans(self):
+        """invalidate_plans for predict_class alone (its weights written outside torch, the
+        rest frozen: training.FinetuneTrainer): the object head's stem and head chains of every
+        plan re-pack on next use; no backbone image is touched."""
+        self._weights_gen += 1
+        owners = list(self._plans.values())
+        if getattr(self, '_train_engine', None) is not None:
+            owners.append(self._train_engine)
+        for o in owners:
+            for c in (o.cls_stem, o.cls_head):
+                if c is not None:
+                    c.invalidate()
+
     def train_engine(self):
         """The float32 tape + backward of this model (backward of grad-enabled calls)."""
         from .training import TrainEngine
@@ -472,6 +485,28 @@ class Model_Object_Classifier_Finetuning(nn.Module):
         if self._train_engine is None or self._train_engine.device != dev:
             self._train_engine = TrainEngine(self, dev)
         return self._train_engine
+
+    def head_engine(self):
+        """The tape + backward of predict_class alone (training.HeadTrainEngine), for a model
+        frozen by pred.freeze_layers_except_object_class_predictor()."""
+        from .training import HeadTrainEngine
+        dev = next(self.parameters()).device
+        eng = getattr(self, '_head_engine', None)
+        if eng is None or eng.device != dev:
+            eng = self._head_engine = HeadTrainEngine(self, dev)
+        return eng
+
+    def invalidate_head_plans(self):
+        """predict_class's weights were written outside torch (training.FinetuneTrainer's
+        optimizer): every packed image made from them -- the inference plans', both train
+        engines' and the head engine's -- is packed again; the frozen rest is left alone."""
+        self.pred.invalidate_head_plans()
+        if self._train_engine is not None:
+            for c in (self._train_engine.cls_stem, self._train_engine.cls_head):
+                if c is not None:
+                    c.invalidate()
+        if getattr(self, '_head_engine', None) is not None:
+            self._head_engine.invalidate()
 
     def forward(self, node_features: List[torch.Tensor], edge_features: List[torch.Tensor],
                 other_features: List[torch.Tensor], edge_index: List[torch.Tensor],

@@ -508,8 +508,10 @@ def detect(detector, node_features: Sequence, edge_features: Sequence, edge_inde
            other_features: Sequence) -> Detections:
     """The detector's batched proposal forward (Model_Inference.forward_frames with
     cluster_node_idx=None) keeping what the object stage needs on the device: the four heads'
-    logits, the proposal clusters' CSR, frame_ptr, the positions, the rcs column and the
-    predicted cluster centres (rg_proposal_centres, computed once by the proposal branch)."""
+    logits, the proposal clusters' CSR, frame_ptr, the positions, the rcs column, the
+    predicted cluster centres (rg_proposal_centres, computed once by the proposal branch) and
+    the forward's outputs with the final node embeddings (``outputs``, ``x``: what
+    training.FinetuneTrainer.step_detections trains the object head from)."""
     torch = _torch()
     from . import engine
     from .gnn_detector import _batch_frames, _set_frames
@@ -547,13 +549,14 @@ def detect(detector, node_features: Sequence, edge_features: Sequence, edge_inde
                       cluster_ptr=out.cluster_ptr, cluster_idx=out.cluster_idx, frame_ptr=fptr,
                       frame_sizes=sizes, xy=other_xy, rcs=nf[:, 1],
                       centres=torch.stack((cx, cy), dim=-1),
-                      meas_noise_cov=detector.meas_noise_cov)
+                      meas_noise_cov=detector.meas_noise_cov, outputs=out, x=out.x)
 
 
 def detect_frames(detector, fb, cfg, dtype: str = 'fp32', cache: Optional[dict] = None):
     """detect() for a ``frontend.frame_batch`` FrameBatch: the graph build, the detector's
     proposal forward under no_grad and the Detections of it -- the forward's outputs
-    (``outputs``, engine.ForwardOutputs; link_cls padded to the pair capacity), the GraphBatch
+    (``outputs``, engine.ForwardOutputs; link_cls padded to the pair capacity; ``x`` its final
+    node embeddings, a buffer of ``cache`` the next call overwrites), the GraphBatch
     (``graph_batch``), frame_ptr, the positions, the rcs column (node_features[:, 1],
     datagen_classifier.py:256) and the predicted centres.  ``detector`` is a Model_Inference
     with its proposal parameters set; ``cache`` keeps workspaces and buffers between batches.
@@ -589,7 +592,8 @@ def detect_frames(detector, fb, cfg, dtype: str = 'fp32', cache: Optional[dict] 
                       cluster_idx=out.cluster_idx, frame_ptr=fb.frame_ptr,
                       frame_sizes=fb.frame_sizes, xy=other_xy, rcs=gb.node_features[:, 1],
                       centres=torch.stack((cx, cy), dim=-1),
-                      meas_noise_cov=detector.meas_noise_cov, outputs=out, graph_batch=gb)
+                      meas_noise_cov=detector.meas_noise_cov, outputs=out, x=out.x,
+                      graph_batch=gb)
 
 
 def detections_object_list(det: Detections, detect_object_by_segmentation_output: bool = True,

@@ -23,6 +23,11 @@ This module only sequences calls and owns buffers.  The batch of frames is one
 disjoint-union graph, as in the forward (engine.forward_batched): every operator is per
 row or per destination, and the losses are sums over rows divided by the batch's row
 counts (loss.py:59-73 on the concatenated predictions), so batching is exact.
+
+Object-head finetuning (gnn/finetuning.py, set_param_for_finetuning_obj_classifier.py) trains
+predict_class alone on a frozen backbone: HeadTrainEngine tapes the head from the no-grad
+proposal forward's node embeddings, FinetuneTrainer is one iteration of it, finetune_sequence
+and validate_finetune_sequence feed it from a SequenceStore.
 """
 from __future__ import annotations
 
@@ -817,6 +822,140 @@ class TrainEngine:
         return 1.0 / deg
 
 
+def finetune_parameters(model) -> List[torch.nn.Parameter]:
+    """The parameters object-head finetuning trains
+    (set_param_for_finetuning_obj_classifier.py:34-39: ``[p for p in parameters() if
+    p.requires_grad]`` after ``pred.freeze_layers_except_object_class_predictor()``), in
+    ``named_parameters`` order.  Host only.  ValueError unless they are exactly the parameters
+    under ``pred.predict_class`` and there is at least one: the head-only step leaves everything
+    else without a gradient, so an unfrozen backbone would silently not train."""
+    named = list(model.named_parameters())
+    prefix = 'pred.predict_class.' if hasattr(model, 'pred') else 'predict_class.'
+    head = [n for n, _ in named if n.startswith(prefix)]
+    want = [n for n, p in named if p.requires_grad]
+    if not head:
+        raise ValueError(f'the model has no parameter under {prefix!r}')
+    if want != head:
+        extra = [n for n in want if not n.startswith(prefix)]
+        frozen = [n for n in head if n not in want]
+        raise ValueError(
+            'object-head finetuning trains exactly the parameters of predict_class '
+            '(pred.freeze_layers_except_object_class_predictor()): '
+            + (f'{len(extra)} trainable outside it (first: {extra[0]}); ' if extra else '')
+            + (f'{len(frozen)} of its own frozen (first: {frozen[0]})' if frozen else ''))
+    return [p for n, p in named if n.startswith(prefix)]
+
+
+N_HEAD_LOSS_SLOTS = 1   # Loss_Object_Class, in the head engine's gradient bucket's tail
+
+
+class HeadTrainEngine(TrainEngine):
+    """Forward-with-tape and backward of ``predict_class`` alone, for a model whose every other
+    parameter is frozen (object-head finetuning, gnn_detector.py:481-519): the steps of
+    TrainEngine.forward_tape from the object head's stem on, fed with the node embeddings the
+    no-grad proposal forward already made (``engine.ForwardOutputs.x``), and the backward down
+    to the stem's weights -- the stem hands no gradient to the frozen backbone.  Nothing sized
+    by the edge count is taped or read.
+
+    The flat bucket holds predict_class's parameters (``finetune_parameters`` order) and one
+    loss slot."""
+
+    def __init__(self, model, device):  # noqa: super().__init__ builds the whole model's chains
+        self.model = model
+        pred = getattr(model, 'pred', model)
+        self.device = torch.device(device)
+        self.ws = Workspaces(self.device)
+        pc = pred.predict_class
+        self.cls_stem = TrainChain(list(pc.stem), self.device, self.ws) if len(pc.stem) else None
+        self.cls_head = TrainChain([pc.pred_cls.head[0], pc.pred_cls.head[1]], self.device,
+                                   self.ws)
+        self.frame_norm = any(c.frame_norm for c in self.chains())
+        self.params = finetune_parameters(model)
+        n = sum(p.numel() for p in self.params)
+        self.flat_bucket = torch.zeros(n + N_HEAD_LOSS_SLOTS, dtype=torch.float32,
+                                       device=self.device)
+        self.flat_grad = self.flat_bucket[:n]
+        self.loss_slots = self.flat_bucket[n:]
+        self.grads: Dict[int, torch.Tensor] = {}
+        o = 0
+        for p in self.params:
+            self.grads[id(p)] = self.flat_grad[o:o + p.numel()].view_as(p)
+            o += p.numel()
+
+    def chains(self):
+        return [c for c in (self.cls_stem, self.cls_head) if c is not None]
+
+    def forward(self, x: torch.Tensor, cluster_ptr, cluster_idx, n_clusters: int,
+                labels: torch.Tensor, frame_ptr=None, n_frames: Optional[int] = None):
+        """x f32 [N, C] (the no-grad forward's ForwardOutputs.x, fp32), the proposal CSR (int32,
+        global node ids), labels int64 [n_clusters], the batch's frame boundaries (int32
+        [n_frames + 1]; layer / group normalisation only).  n_clusters >= 1.
+        Returns (loss f32 [1], accuracy f32 [1], tape)."""
+        lib = nat.lib()
+        dev = self.device
+        st = nat.stream_ptr(dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        x = _f32(x)
+        N, C, ncl = int(x.shape[0]), int(x.shape[1]), int(n_clusters)
+        if ncl < 1:
+            raise ValueError('the head-only step needs at least one proposal')
+        if labels.dtype != torch.int64 or int(labels.shape[0]) < ncl:
+            raise TypeError('labels must be int64 [n_clusters]')
+        nsegs = csegs = None
+        if self.frame_norm:
+            if frame_ptr is None or n_frames is None:
+                raise ValueError('layer / group normalisation needs the batch\'s frame '
+                                 'boundaries (frame_ptr, n_frames)')
+            # the rows TrainEngine's g.segs('node') / engine.cluster_segs give
+            nsegs = (frame_ptr.to(torch.int32).contiguous(), int(n_frames))
+            csegs = engine.cluster_segs(cluster_ptr, cluster_idx, ncl, nsegs[0], nsegs[1])
+        T = {}
+        if self.cls_stem is not None:
+            h = torch.empty((N, self.cls_stem.out_dim), **f32)
+            T['cls_stem'] = self.cls_stem.forward(N, h, x, C, segs=nsegs)
+        else:
+            h = x
+        pooled = torch.empty((ncl, h.shape[1]), **f32)
+        engine.segment_reduce(h, cluster_ptr, ncl, 'max', pooled, idx=cluster_idx)
+        obj = torch.empty((ncl, self.cls_head.out_dim), **f32)
+        T['cls_head'] = self.cls_head.forward(ncl, obj, pooled, pooled.shape[1], segs=csegs)
+        lab = labels.contiguous()
+        out = torch.empty(2, **f32)
+        nat.check(lib.rg_cross_entropy(obj.data_ptr(), obj.stride(0), lab.data_ptr(), ncl,
+                                       obj.shape[1], out.data_ptr(), out.data_ptr() + 4, st),
+                  'rg_cross_entropy')
+        T.update(h=h, obj=obj, labels=lab, cptr=cluster_ptr, cidx=cluster_idx, ncl=ncl, N=N)
+        return out[:1], out[1:], T
+
+    def backward(self, T: dict, g_loss: torch.Tensor, zero_grads: bool = True):
+        """Gradients of g_loss[0] * loss into self.flat_grad."""
+        lib = nat.lib()
+        st = nat.stream_ptr(self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        if zero_grads:
+            self.flat_grad.zero_()
+        G = self.grads
+        obj, h, ncl, N = T['obj'], T['h'], T['ncl'], T['N']
+        gl = g_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_o = torch.empty_like(obj)
+        nat.check(lib.rg_cross_entropy_backward(obj.data_ptr(), obj.stride(0),
+                                                T['labels'].data_ptr(), ncl, obj.shape[1],
+                                                gl.data_ptr(), d_o.data_ptr(), d_o.stride(0), st),
+                  'rg_cross_entropy_backward')
+        if self.cls_stem is None:     # the pooled rows are frozen embeddings: the head alone
+            self.cls_head.backward(T['cls_head'], d_o, G)
+            return
+        d_pooled = torch.empty((ncl, h.shape[1]), **f32)
+        self.cls_head.backward(T['cls_head'], d_o, G, din=d_pooled)
+        dh = torch.zeros((N, h.shape[1]), **f32)
+        nat.check(lib.rg_segment_max_backward(h.data_ptr(), h.stride(0), h.shape[1],
+                                              T['cptr'].data_ptr(), T['cidx'].data_ptr(), ncl,
+                                              d_pooled.data_ptr(), d_pooled.stride(0),
+                                              dh.data_ptr(), dh.stride(0), st),
+                  'rg_segment_max_backward')
+        self.cls_stem.backward(T['cls_stem'], dh, G)
+
+
 class _TrainStep(torch.autograd.Function):
     """Loss_Graph values as an autograd node over every parameter: loss.backward()
     (training.py:77) runs TrainEngine.backward and hands torch the flat gradients."""
@@ -1184,3 +1323,216 @@ def train_sequence(store, trainer: RadarGNNTrainer, cfg, indices, window_size: i
         return (torch.empty((0, N_LOSS_SLOTS), dtype=torch.float32, device=dev),
                 torch.empty((0, 3), dtype=torch.float32, device=dev))
     return torch.stack(losses), torch.stack(accs)
+
+
+# ------------------------------------------------------------------ object-head finetuning
+class FinetuneTrainer:
+    """One data-parallel iteration of object-head finetuning (finetuning.py:47-64 for one
+    rank's batch) from the detector's own no-grad proposal forward: majority labels of the
+    proposals -> HeadTrainEngine forward and backward (predict_class alone, from the forward's
+    node embeddings) -> gradient all-reduce -> one fused optimizer launch.  The host reads
+    nothing back beyond what the proposal forward (``engine.propose_clusters``) already did.
+
+    ``model_finetuning`` is a gnn_detector.Model_Object_Classifier_Finetuning after
+    ``pred.freeze_layers_except_object_class_predictor()``; the optimizer takes
+    ``finetune_parameters(model)`` only (set_param_for_finetuning_obj_classifier.py:36-41:
+    cfg.optim_finetuning picks SGD with momentum 0.9 or AdamW, lr and weight decay from
+    cfg.learning_rate_finetuning / cfg.weight_decay_finetuning, ``lr_scheduler = None``: no
+    milestones).  skip_batch holds as in RadarGNNTrainer: the loss rides in the bucket's tail,
+    and the optimizer kernel skips the update on every rank when the summed loss is NaN.  Every
+    step ends in ``model.invalidate_head_plans``: each packed image made from the head is
+    packed again, no backbone image is touched.
+
+    ``world > 1``: ``broadcast_parameters`` acts on the optimizer's flat buffer, which holds
+    predict_class only -- the frozen weights are never sent, so every rank must have loaded the
+    same checkpoint."""
+
+    def __init__(self, model_finetuning, cfg, world: int = 1, lr: Optional[float] = None,
+                 weight_decay: Optional[float] = None, optim: Optional[str] = None,
+                 momentum: float = 0.9):
+        if model_finetuning.pred.compute_dtype != 'fp32':
+            raise NotImplementedError('object-head finetuning runs in float32 (the reference '
+                                      'precision); set pred.compute_dtype = "fp32"')
+        self.model = model_finetuning
+        self.cfg = cfg
+        self.world = world
+        lr = cfg.learning_rate_finetuning if lr is None else lr
+        wd = cfg.weight_decay_finetuning if weight_decay is None else weight_decay
+        optim = cfg.optim_finetuning if optim is None else optim
+        params = finetune_parameters(model_finetuning)
+        if optim == 'sgd':
+            self.opt = FusedSGD(params, lr, momentum, wd,
+                                on_update=model_finetuning.invalidate_head_plans, milestones=())
+        elif optim == 'adamw':
+            self.opt = FusedAdamW(params, lr, wd, on_update=model_finetuning.invalidate_head_plans,
+                                  milestones=())
+        else:
+            raise ValueError(f'optim {optim!r}: the reference configures sgd or adamw')
+        broadcast_parameters(self.opt.flat, world)
+        model_finetuning.invalidate_head_plans()
+        self.one = torch.ones(1, dtype=torch.float32, device=self.opt.flat.device)
+
+    @property
+    def engine(self) -> HeadTrainEngine:
+        """The model's head engine (packed on first use: a HIP device only)."""
+        return self.model.head_engine()
+
+    def _join_skipped(self):
+        """This rank has nothing to train on: zero gradients and NaN in the loss slot, so the
+        summed loss is NaN on every rank and every rank skips the step (skip_batch)."""
+        eng = self.engine
+        eng.flat_grad.zero_()
+        eng.loss_slots.fill_(float('nan'))
+        scale = allreduce_gradients(eng.flat_bucket, self.world)
+        self.opt.step(eng.flat_grad, grad_scale=scale, losses=eng.loss_slots)
+
+    def step_detections(self, det, node_class):
+        """One iteration on an ``objects.Detections`` that carries ``outputs.x`` (objects.detect
+        / detect_frames of ``model.pred``, detector dtype fp32) and the nodes' ground-truth
+        classes [N] (any dtype holding integers).  Returns (loss f32 [1], accuracy f32 [1]) on
+        the device; a NaN loss: the update was skipped and the step not counted.  A node class
+        outside [0, num_classes) puts NaN in the loss slot, so that step is skipped too.
+
+        ``det`` None (a batch without a frame) or without a proposal -- the reference stacks
+        an empty list there: with ``world == 1`` nothing runs and None is returned; with
+        ``world > 1`` the rank still joins the all-reduce, with zero gradients and NaN in its
+        loss slot, so every rank skips and none waits for a missing peer; None is returned."""
+        from . import objects
+        ncl = 0 if det is None else int(det.cluster_ptr.numel()) - 1
+        if ncl <= 0:
+            if self.world > 1:
+                self._join_skipped()
+            return None
+        x = det.outputs.x
+        if x.dtype != torch.float32:
+            raise NotImplementedError(f'the detector forward ran in {x.dtype}; the head-only '
+                                      'step takes its float32 embeddings (dtype "fp32")')
+        if int(node_class.shape[0]) != int(x.shape[0]):
+            raise ValueError(f'{int(node_class.shape[0])} node classes for {int(x.shape[0])} '
+                             'nodes')
+        eng = self.engine
+        dev = eng.device
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        gt = objects.majority_class(node_class, det.cluster_ptr, det.cluster_idx,
+                                    int(self.cfg.num_classes), bad)
+        loss, acc, tape = eng.forward(x, det.cluster_ptr, det.cluster_idx, ncl, gt,
+                                      det.frame_ptr, len(det.frame_sizes))
+        eng.backward(tape, self.one)
+        eng.loss_slots.copy_(torch.where(bad > 0, torch.full_like(loss, float('nan')), loss))
+        scale = allreduce_gradients(eng.flat_bucket, self.world)
+        self.opt.step(eng.flat_grad, grad_scale=scale, losses=eng.loss_slots)
+        return loss, acc
+
+    def save(self, path):
+        """save_model_weights (finetuning.py:84) on rank 0: the reference's state_dict keys."""
+        rank = 0
+        if self.world > 1:
+            import torch.distributed as dist
+            rank = dist.get_rank()
+        if rank == 0:
+            torch.save(self.model.state_dict(), path)
+
+
+def _finetune_batches(indices, batch_windows):
+    if int(batch_windows) < 1:
+        raise ValueError(f'batch_windows={batch_windows} < 1')
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    for k, i0 in enumerate(range(0, int(idx.shape[0]), int(batch_windows))):
+        yield k, idx[i0:i0 + int(batch_windows)]
+
+
+def _finetune_detections(store, detector, cfg, pos, window_size, flags, cache):
+    """One batch of sliding positions to (Detections or None, FrameBatch): store.windows ->
+    dynamic_frame (flipped by flags) -> frame_batch -> objects.detect_frames."""
+    from . import frontend, objects
+    ransac = bool(getattr(cfg, 'reject_static_meas_by_ransac', False))
+    win = store.windows(pos, window_size)
+    # (the head reads the class labels only: the offsets' mean is left at the default)
+    dd, gd = frontend.dynamic_frame(win, ransac, with_keys=True, flip=flags)
+    fb = frontend.frame_batch(dd, gd)
+    return objects.detect_frames(detector, fb, cfg, cache=cache), fb
+
+
+def finetune_sequence(store, trainer: FinetuneTrainer, cfg, indices, window_size: int = 10,
+                      batch_windows: int = 64, augmentation: Optional[bool] = None,
+                      on_step=None):
+    """Object-head finetuning from a ``sequence.SequenceStore``: the sliding positions
+    ``indices``, in the caller's order, in batches of ``batch_windows``; each batch goes
+    ``store.windows`` -> ``frontend.dynamic_frame`` (with the x-axis flip when ``augmentation``,
+    default cfg.dataset_augmentation; the flags from ``frontend.draw_flips``, numpy's global
+    generator, drawn as ``train_sequence`` draws them) -> ``frontend.frame_batch`` -> graph
+    build and the model's own proposal forward under no_grad (``objects.detect_frames`` on
+    ``trainer.model.pred``) -> ``FinetuneTrainer.step_detections`` with the batch's node
+    classes.  No host work per window and no per-frame list; per batch the host waits only
+    where ``select_dynamic``, ``frame_batch`` and ``propose_clusters`` do.
+    ``on_step(step index, positions, flags or None, (loss, accuracy) or None, Detections or
+    None)`` is called after every batch (a batch without a frame or a proposal goes to
+    step_detections too, so a rank of several still joins the step's all-reduce).  Returns
+    (losses f32 [steps], accuracies f32 [steps]) on the device: one entry per batch that had a
+    proposal (a skipped NaN step keeps its entry)."""
+    from . import frontend
+    augmentation = bool(cfg.dataset_augmentation if augmentation is None else augmentation)
+    detector = trainer.model.pred
+    cache: dict = {}
+    losses, accs = [], []
+    for k, pos in _finetune_batches(indices, batch_windows):
+        flags = frontend.draw_flips(int(pos.shape[0])) if augmentation else None
+        det, fb = _finetune_detections(store, detector, cfg, pos, window_size, flags, cache)
+        out = trainer.step_detections(det, fb.labels['class_labels'] if det is not None else None)
+        if out is not None:
+            losses.append(out[0])
+            accs.append(out[1])
+        if on_step is not None:
+            on_step(k, pos, flags, out, det)
+    dev = trainer.opt.flat.device
+    if not losses:
+        return (torch.empty(0, dtype=torch.float32, device=dev),
+                torch.empty(0, dtype=torch.float32, device=dev))
+    return torch.cat(losses), torch.cat(accs)
+
+
+def average_counted(losses, values=None):
+    """finetuning.py:86-101's rule for what the validation trackers average: an iteration
+    counts when its loss is > 0 (``if loss > 0:``), which leaves out 0, negatives and NaN.
+    Returns (mean of ``values`` -- default the losses themselves -- over the iterations that
+    count, their number); (nan, 0) when none counts.  Host only."""
+    lo = np.asarray(losses, dtype=np.float64).reshape(-1)
+    va = lo if values is None else np.asarray(values, dtype=np.float64).reshape(-1)
+    if va.shape != lo.shape:
+        raise ValueError(f'{va.shape[0]} values for {lo.shape[0]} losses')
+    with np.errstate(invalid='ignore'):
+        keep = lo > 0
+    if not keep.any():
+        return float('nan'), 0
+    return float(np.mean(va[keep])), int(keep.sum())
+
+
+def validate_finetune_sequence(store, model_finetuning, cfg, indices, window_size: int = 10,
+                               batch_windows: int = 64):
+    """The validation pass of finetuning.py:86-101 over a sequence: the walk of
+    finetune_sequence without the flip, under no_grad; Loss_Object_Class and the accuracy
+    (``rg_cross_entropy``) on the proposal forward's own object logits against the proposals'
+    majority labels -- no tape.  Returns (mean loss, mean accuracy, n) over the batches whose
+    loss is > 0 (``average_counted``): (nan, nan, 0) when none counts.  One read-back, at the
+    end.  Weights, optimizer state and applied steps are untouched."""
+    from . import objects
+    from .loss import _ce_forward
+    detector = model_finetuning.pred
+    cache: dict = {}
+    rows = []
+    with torch.no_grad():
+        for _, pos in _finetune_batches(indices, batch_windows):
+            det, fb = _finetune_detections(store, detector, cfg, pos, window_size, None, cache)
+            ncl = 0 if det is None else int(det.cluster_ptr.numel()) - 1
+            if ncl <= 0:
+                continue
+            gt = objects.majority_class(fb.labels['class_labels'], det.cluster_ptr,
+                                        det.cluster_idx, int(cfg.num_classes))
+            logits = det.obj_cls.to(torch.float32).contiguous()
+            rows.append(torch.stack(_ce_forward(logits, gt)))
+    if not rows:
+        return float('nan'), float('nan'), 0
+    vals = torch.stack(rows).cpu().numpy()
+    loss, n = average_counted(vals[:, 0])
+    acc, _ = average_counted(vals[:, 0], vals[:, 1])
+    return loss, acc, n
