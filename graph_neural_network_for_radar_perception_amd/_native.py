@@ -136,6 +136,8 @@ _SIGNATURES = {
     # sequence store (sequence.hip)
     'rg_sequence_windows': (_I, [ctypes.POINTER(rg_sequence), _P, _I, _I, _L,
                                  ctypes.POINTER(rg_window_batch), _P]),
+    'rg_sequence_set_windows': (_I, [_P, _I, _I, _P, _I, _I, _L,
+                                     ctypes.POINTER(rg_window_batch), _P]),
     # training feed (training_feed.hip)
     'rg_frontend_flip': (_I, [_P, _P, _P, _I, _P, _I, _P]),
     'rg_train_labels': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P]),

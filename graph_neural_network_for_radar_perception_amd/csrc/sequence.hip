@@ -9,6 +9,12 @@
 // lanes of a wave read and write consecutive rows of every field: coalesced both ways).
 // ~52 B per measurement; at 64 windows x 10 scans x ~134 rows the launches, not HBM, set
 // the time.
+//
+// rg_sequence_set_windows (sequence.py, SequenceSet) cuts a batch whose windows come from
+// several sequences -- the batch a shuffling loader over create_sequences_info_list's
+// metadata (read_data.py:330-396) hands out -- with the same two kernels: they are templates
+// over where window b's sequence descriptor comes from, the kernel arguments (OneSequence) or
+// a device table indexed by the window's sequence id (SequenceTable).
 #include "rg_common.h"
 
 #include <math.h>
@@ -36,10 +42,41 @@ __device__ __forceinline__ SceneRange scene_range(const rg_sequence& q, long s) 
   return r;
 }
 
+// Where the windows of a batch come from.  at(b, q, scene): the descriptor of the sequence
+// window b is cut from and the window's first scene (false: no such sequence, every
+// window-scan of b is empty); key_offset(b): what the non-zero track keys of window b are
+// shifted by.  q is a copy, so that the one sequence of the arguments stays in the kernel's
+// argument registers; of a table's descriptor only the fields that are used are loaded.
+struct OneSequence {  // rg_sequence_windows: every window from the sequence in the arguments
+  rg_sequence q;
+  const int* first;
+  __device__ __forceinline__ bool at(int b, rg_sequence& out, long& scene) const {
+    scene = first[b];
+    out = q;
+    return true;
+  }
+  __device__ __forceinline__ int key_offset(int b) const { return b * q.n_tracks; }
+};
+
+struct SequenceTable {  // rg_sequence_set_windows: window b from seqs[win[2b]], a device table
+  const rg_sequence* seqs;
+  const int* win;
+  int n_seq, key_stride;
+  __device__ __forceinline__ bool at(int b, rg_sequence& out, long& scene) const {
+    const int id = win[2 * (long)b];
+    scene = win[2 * (long)b + 1];
+    if (id < 0 || id >= n_seq) return false;  // clamped before any read
+    out = seqs[id];
+    return true;
+  }
+  __device__ __forceinline__ int key_offset(int b) const { return b * key_stride; }
+};
+
 // One workgroup: exclusive scan of the n_ws = n_windows * W scene sizes, 256 at a time with
 // a running carry, and everything that exists once per window-scan.
+template <class Source>
 __global__ __launch_bounds__(SEQ_SCAN_THREADS) void sequence_scan_kernel(
-    rg_sequence q, const int* __restrict__ win_first, int n_windows, int W, rg_window_batch o) {
+    Source src, int n_windows, int W, rg_window_batch o) {
   __shared__ int wsum[SEQ_SCAN_THREADS / 64];
   const int n_ws = n_windows * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -50,7 +87,9 @@ __global__ __launch_bounds__(SEQ_SCAN_THREADS) void sequence_scan_kernel(
     const bool live = j < n_ws;
     const int b = live ? j / W : 0, w = j - b * W;
     SceneRange r = {0, 0, -1, -1};
-    if (live) r = scene_range(q, (long)win_first[b] + w);
+    rg_sequence q = {};
+    long scene = 0;
+    if (live && src.at(b, q, scene)) r = scene_range(q, scene + w);
     int incl = r.count;
     for (int d = 1; d < 64; d <<= 1) {
       const int v = __shfl_up(incl, d);
@@ -68,7 +107,7 @@ __global__ __launch_bounds__(SEQ_SCAN_THREADS) void sequence_scan_kernel(
       o.scan_ptr[j] = excl;
       o.scan_ref[j] = b * W + W - 1;
       if (w == 0) o.win_ptr[b] = excl;
-      const bool ok = r.sensor >= 0 && r.odo >= 0;
+      const bool ok = r.sensor >= 0 && r.odo >= 0;  // only with a descriptor in q
       for (int c = 0; c < 3; ++c) o.mount[3 * (long)j + c] = ok ? q.mount[3 * r.sensor + c] : nan;
       for (int c = 0; c < 5; ++c)
         o.odometry[5 * (long)j + c] = ok ? q.odometry[5 * (long)r.odo + c] : nan;
@@ -83,19 +122,24 @@ __global__ __launch_bounds__(SEQ_SCAN_THREADS) void sequence_scan_kernel(
 }
 
 // One wave per window-scan j: its rows [scan_ptr[j], scan_ptr[j + 1]) from the scene's rows.
+// j is formed through readfirstlane, so the window's entry and its sequence's descriptor are
+// read with scalar loads, once per wave and before the first store.
+template <class Source>
 __global__ __launch_bounds__(64 * SEQ_WAVES) void sequence_gather_kernel(
-    rg_sequence q, const int* __restrict__ win_first, int n_windows, int W, long capacity,
-    rg_window_batch o) {
-  const int j = blockIdx.x * SEQ_WAVES + (threadIdx.x >> 6);
+    Source src, int n_windows, int W, long capacity, rg_window_batch o) {
+  const int j = blockIdx.x * SEQ_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (j >= n_windows * W) return;
   const int lane = threadIdx.x & 63;
   const int b = j / W, w = j - b * W;
-  const SceneRange r = scene_range(q, (long)win_first[b] + w);
+  rg_sequence q;
+  long scene;
+  if (!src.at(b, q, scene)) return;
+  const SceneRange r = scene_range(q, scene + w);
   const int m0 = o.scan_ptr[j];
   // the scan's own size bounds the source rows, the capacity the output rows
   const long lim = min((long)m0 + r.count, capacity);
   if (m0 < 0) return;
-  const int key_off = b * q.n_tracks;
+  const int key_off = src.key_offset(b);
   for (int i = lane; i < r.count; i += 64) {
     const long m = (long)m0 + i;
     if (m >= lim) break;
@@ -114,6 +158,33 @@ __global__ __launch_bounds__(64 * SEQ_WAVES) void sequence_gather_kernel(
     const int k = q.track_key[s];
     o.track_key[m] = k == 0 ? 0 : k + key_off;
   }
+}
+
+// the two launches both entry points make
+template <class Source>
+static int launch_windows(const Source& src, int n_windows, int W, long capacity, bool rows,
+                          const rg_window_batch& out, hipStream_t st) {
+  sequence_scan_kernel<Source><<<1, SEQ_SCAN_THREADS, 0, st>>>(src, n_windows, W, out);
+  RG_LAUNCH_CHECK();
+  const int n_ws = n_windows * W;
+  if (n_ws > 0 && capacity > 0 && rows) {
+    sequence_gather_kernel<Source><<<ceil_div(n_ws, SEQ_WAVES), 64 * SEQ_WAVES, 0, st>>>(
+        src, n_windows, W, capacity, out);
+    RG_LAUNCH_CHECK();
+  }
+  return RG_OK;
+}
+
+// what both entry points require of the outputs
+static int check_outputs(const char* who, const rg_window_batch* out, long capacity) {
+  RG_REQUIRE(out->scan_ptr && out->scan_ref && out->win_ptr && out->mount && out->odometry,
+             RG_ERR_ARG, "%s: null per-scan output", who);
+  RG_REQUIRE(capacity == 0 ||
+                 (out->meas_scan && out->src_row && out->x_cc && out->y_cc && out->azimuth_sc &&
+                  out->vr && out->vr_compensated && out->rcs && out->timestamp &&
+                  out->sensor_id && out->label_id && out->track_key),
+             RG_ERR_ARG, "%s: null per-measurement output", who);
+  return RG_OK;
 }
 
 }  // namespace rg
@@ -143,23 +214,30 @@ extern "C" int rg_sequence_windows(const rg_sequence* seq, const int* win_first,
                   seq->rcs && seq->timestamp && seq->sensor_id && seq->label_id &&
                   seq->track_key),
              RG_ERR_ARG, "rg_sequence_windows: null measurement field");
-  RG_REQUIRE(out->scan_ptr && out->scan_ref && out->win_ptr && out->mount && out->odometry,
-             RG_ERR_ARG, "rg_sequence_windows: null per-scan output");
-  RG_REQUIRE(capacity == 0 ||
-                 (out->meas_scan && out->src_row && out->x_cc && out->y_cc && out->azimuth_sc &&
-                  out->vr && out->vr_compensated && out->rcs && out->timestamp &&
-                  out->sensor_id && out->label_id && out->track_key),
-             RG_ERR_ARG, "rg_sequence_windows: null per-measurement output");
+  if (int rc = check_outputs("rg_sequence_windows", out, capacity)) return rc;
   RG_REQUIRE(((uintptr_t)seq->scenes & 15) == 0, RG_ERR_ARG,
              "rg_sequence_windows: the scene table must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  sequence_scan_kernel<<<1, SEQ_SCAN_THREADS, 0, st>>>(*seq, win_first, n_windows, W, *out);
-  RG_LAUNCH_CHECK();
-  const int n_ws = n_windows * W;
-  if (n_ws > 0 && capacity > 0 && seq->n_meas > 0) {
-    sequence_gather_kernel<<<ceil_div(n_ws, SEQ_WAVES), 64 * SEQ_WAVES, 0, st>>>(
-        *seq, win_first, n_windows, W, capacity, *out);
-    RG_LAUNCH_CHECK();
-  }
-  return RG_OK;
+  const OneSequence src = {*seq, win_first};
+  return launch_windows(src, n_windows, W, capacity, seq->n_meas > 0, *out, (hipStream_t)stream);
+}
+
+extern "C" int rg_sequence_set_windows(const rg_sequence* seqs, int n_seq, int key_stride,
+                                       const int* win, int n_windows, int W, long capacity,
+                                       const rg_window_batch* out, void* stream) {
+  RG_REQUIRE(seqs && out && win, RG_ERR_ARG, "rg_sequence_set_windows: null argument");
+  RG_REQUIRE(n_seq >= 1 && key_stride >= 0, RG_ERR_ARG,
+             "rg_sequence_set_windows: n_seq=%d key_stride=%d", n_seq, key_stride);
+  RG_REQUIRE(W >= 1 && n_windows >= 0 && capacity >= 0, RG_ERR_ARG,
+             "rg_sequence_set_windows: W=%d n_windows=%d capacity=%ld", W, n_windows, capacity);
+  RG_REQUIRE((long)n_windows * W < 0x7fffffffL, RG_ERR_ARG,
+             "rg_sequence_set_windows: %d windows of %d scans", n_windows, W);
+  RG_REQUIRE((long)n_windows * key_stride < 0x7fffffffL, RG_ERR_ARG,
+             "rg_sequence_set_windows: %d windows x key stride %d leave int32", n_windows,
+             key_stride);
+  if (int rc = check_outputs("rg_sequence_set_windows", out, capacity)) return rc;
+  RG_REQUIRE(((uintptr_t)seqs & 7) == 0, RG_ERR_ARG,
+             "rg_sequence_set_windows: the descriptor table must be 8-byte aligned");
+  // the descriptors lie on the device: their sizes and tables are clamped where they are read
+  const SequenceTable src = {seqs, win, n_seq, key_stride};
+  return launch_windows(src, n_windows, W, capacity, true, *out, (hipStream_t)stream);
 }

@@ -11,6 +11,10 @@ native call (``rg_sequence_windows``, csrc/sequence.hip) into the batch ``ScanWi
   sliding_windows    create_dataset_sliding_window (read_data.py:203-224)
   SequenceStore      the arrays of get_sequence_data on the device; ``windows`` is
                      extract_frame's slicing for a batch of sliding positions
+  SequenceSet        several stores as the one window list of create_sequences_info_list
+                     (read_data.py:330-396); ``windows`` cuts a batch from any mix of them
+                     (``rg_sequence_set_windows``)
+  dataset_indices    the stride and shuffle of set_param_for_training_gnn.py:81-88 on indices
 
 Nothing here reads a file: the caller parses scenes.json / sensors.json and reads the .h5
 arrays.
@@ -253,3 +257,119 @@ class SequenceStore:
         w = ScanWindow(arrays, scan_ptr, mount, odo, key, B * self.n_tracks, scan_ref, win_ptr)
         w.meas_scan, w.src_row = meas_scan, src_row
         return w
+
+
+class SequenceSet:
+    """Several sequences on one device as ONE list of sliding windows, in the order of
+    ``create_sequences_info_list`` (read_data.py:330-396): the stores in the given order and,
+    within a store, the sliding positions in ascending order; a store with fewer than W scenes
+    contributes no window.  ``windows`` cuts a batch from any mix of the stores in one native
+    call (``rg_sequence_set_windows``), so the set goes wherever a ``SequenceStore`` goes
+    (``n_windows`` and ``windows`` are all the sequence loops read).
+
+    Track keys: batch slot b gets the keys ``k + b * T_max`` with ``T_max`` the largest
+    ``n_tracks`` of the stores (at least 1), so its non-zero keys lie in
+    ``(b * T_max, (b + 1) * T_max]`` and within a window they order and group the measurements
+    as the window's own store's keys do (the module docstring's argument, unchanged).
+
+    Sharding a batch across ranks stays with the caller, who passes each rank its indices."""
+
+    def __init__(self, stores: Sequence[SequenceStore]):
+        import torch
+        self.stores = list(stores)
+        if not self.stores:
+            raise ValueError('a SequenceSet needs at least one SequenceStore')
+        self.device = self.stores[0].device
+        for i, s in enumerate(self.stores):
+            if s.device != self.device:
+                raise ValueError(f'store {i} lies on {s.device}, store 0 on {self.device}')
+        self.n_tracks = max(max(s.n_tracks for s in self.stores), 1)      # T_max
+        table = (nat.rg_sequence * len(self.stores))(*(s._seq for s in self.stores))
+        raw = np.frombuffer(bytes(table), dtype=np.uint8).copy()
+        self._table = torch.from_numpy(raw).to(self.device)    # the descriptors, uploaded once
+
+    def _starts(self, window_size: int) -> np.ndarray:
+        """Global index of every store's first window, and the total: int64 [n_stores + 1]."""
+        counts = [s.n_windows(window_size) for s in self.stores]
+        return np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+
+    def n_windows(self, window_size: int) -> int:
+        return int(self._starts(window_size)[-1])
+
+    def locate(self, indices, window_size: int):
+        """Global windows to (store index int64 [B], sliding position int64 [B]), host."""
+        starts = self._starts(window_size)
+        nw = int(starts[-1])
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        bad = idx[(idx < 0) | (idx >= nw)]
+        if bad.size:
+            raise IndexError(f'window {int(bad[0])} outside [0, {nw}) for window_size='
+                             f'{window_size}')
+        seq = np.searchsorted(starts, idx, side='right').astype(np.int64) - 1
+        return seq, idx - starts[seq]
+
+    def host_window(self, g: int, window_size: int = 10) -> dict:
+        """Global window g as host arrays: the located store's ``host_window``."""
+        seq, pos = self.locate([g], window_size)
+        return self.stores[int(seq[0])].host_window(int(pos[0]), window_size)
+
+    def windows(self, indices: Sequence[int], window_size: int = 10):
+        """The global windows ``indices`` (host integers; any mix of the stores, repeats
+        allowed) as ONE batch ``frontend.ScanWindow``, as ``SequenceStore.windows`` gives it:
+        one small asynchronous upload (store, position per window) and one native call, no
+        host synchronisation.  The window carries ``meas_scan``, ``src_row`` (the row inside
+        the window's own store) and ``win_seq`` (int32 [B]: the window's store)."""
+        import torch
+        from .frontend import ScanWindow
+        seq, pos = self.locate(indices, window_size)
+        W, B, T = int(window_size), int(seq.shape[0]), self.n_tracks
+        if B == 0:
+            raise ValueError('no window requested')
+        if B * T > INT32_MAX or B * W > INT32_MAX:
+            raise ValueError(f'{B} windows x {T} tracks (x {W} scans) leave int32')
+        total = 0
+        for s in np.unique(seq):
+            p, prefix = pos[seq == s], self.stores[int(s)].prefix
+            total += int((prefix[p + W] - prefix[p]).sum())
+        if total > INT32_MAX:
+            raise ValueError(f'{total} measurements in one batch do not fit int32 offsets')
+        dev = self.device
+        win = _upload_small(np.stack((seq, pos), axis=1).astype(np.int32), dev)
+        n_ws = B * W
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        i64 = dict(dtype=torch.int64, device=dev)
+        arrays = {k: torch.empty(total, **f32) for k in F32_FIELDS}
+        for k in ('timestamp', 'sensor_id', 'label_id'):
+            arrays[k] = torch.empty(total, **i64)
+        scan_ptr, scan_ref = torch.empty(n_ws + 1, **i32), torch.empty(n_ws, **i32)
+        win_ptr = torch.empty(B + 1, **i32)
+        mount = torch.empty((n_ws, 3), dtype=torch.float64, device=dev)
+        odo = torch.empty((n_ws, 5), dtype=torch.float64, device=dev)
+        key, meas_scan, src_row = (torch.empty(total, **i32) for _ in range(3))
+        out = nat.rg_window_batch(
+            scan_ptr=scan_ptr.data_ptr(), scan_ref=scan_ref.data_ptr(),
+            win_ptr=win_ptr.data_ptr(), mount=mount.data_ptr(), odometry=odo.data_ptr(),
+            meas_scan=meas_scan.data_ptr(), src_row=src_row.data_ptr(),
+            track_key=key.data_ptr(), **{k: v.data_ptr() for k, v in arrays.items()})
+        nat.check(nat.lib().rg_sequence_set_windows(
+            self._table.data_ptr(), len(self.stores), T, win.data_ptr(), B, W, total,
+            ctypes.byref(out), nat.stream_ptr(dev)), 'rg_sequence_set_windows')
+        w = ScanWindow(arrays, scan_ptr, mount, odo, key, B * T, scan_ref, win_ptr)
+        w.meas_scan, w.src_row, w.win_seq = meas_scan, src_row, win[:, 0]
+        return w
+
+
+def dataset_indices(n: int, num_samples: int = 0, shuffle: bool = False) -> np.ndarray:
+    """set_param_for_training_gnn.py:81-88 (and :102-109) on the indices of a metadata list
+    of n windows: with ``num_samples > 0`` every ``int(n / num_samples)``-th window from the
+    first, then with ``shuffle`` the ``np.random.shuffle`` permutation of an ``arange`` drawn
+    from numpy's global generator.  int64, host."""
+    idx = np.arange(int(n), dtype=np.int64)
+    if num_samples > 0:
+        idx = idx[0::int(int(n) / num_samples)]
+    if shuffle:
+        order = np.arange(len(idx))
+        np.random.shuffle(order)
+        idx = idx[order]
+    return idx

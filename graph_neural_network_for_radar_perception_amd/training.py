@@ -24,6 +24,12 @@ disjoint-union graph, as in the forward (engine.forward_batched): every operator
 row or per destination, and the losses are sums over rows divided by the batch's row
 counts (loss.py:59-73 on the concatenated predictions), so batching is exact.
 
+The loop around the step (training.py:66-134): train_sequence feeds step_frames from a
+SequenceStore or a SequenceSet in the caller's order; train_dataset is train_model's iteration
+structure over a training and a validation set -- shuffled_batches (the endless shuffling
+loader), validate_frames / validate_sequence (the no-grad validation pass) and
+RadarGNNTrainer.save every val_period iterations.
+
 Object-head finetuning (gnn/finetuning.py, set_param_for_finetuning_obj_classifier.py) trains
 predict_class alone on a frozen backbone: HeadTrainEngine tapes the head from the no-grad
 proposal forward's node embeddings, FinetuneTrainer is one iteration of it, finetune_sequence
@@ -1285,6 +1291,56 @@ class RadarGNNTrainer:
         self.opt.step(eng.flat_grad, grad_scale=scale, losses=eng.loss_slots)
         return losses, acc, gb
 
+    def validate_frames(self, batch):
+        """The validation forward of train_model (training.py:111-121) for a
+        ``frontend.frame_batch(dd, gd)`` batch made ``with_keys=True``: ``step_frames`` up to
+        Loss_Graph under no_grad -- the same graph build, ``training_labels`` and forward
+        kernels on the same values, so for the same weights its (losses f32 [4], accuracies
+        f32 [3]) equal ``step_frames``' bit for bit -- and nothing after it: no backward, no
+        all-reduce, no optimizer launch; the tape is dropped.  One device-to-host copy (the
+        three sizes).  None for an empty batch, on every rank (nothing to join)."""
+        from .graph_features import build_graph_batch
+        if batch.n_frames == 0:
+            return None
+        with torch.no_grad():
+            gb = build_graph_batch(batch, self.cfg, ws_cache=self.ws_cache)
+            g = gb.graph
+            labels = training_labels(batch, gb, self.cfg, self.ws_cache)
+            sizes = torch.cat((gb.n_edges_dev.reshape(1), g.n_pairs_dev.reshape(1),
+                               labels['n_clusters_dev'].reshape(1))).tolist()
+            g.n_edges, g.n_pairs, ncl = (int(v) for v in sizes)
+            losses, acc, _ = self.engine.forward(gb.node_features, gb.edge_features, g,
+                                                 labels['cluster_ptr'], labels['cluster_idx'],
+                                                 ncl, labels)
+        return losses, acc
+
+    def save(self, path):
+        """save_model_weights (training.py:15-18, :104) on rank 0: the Model_Training
+        state_dict under the reference's keys."""
+        rank = 0
+        if self.world > 1:
+            import torch.distributed as dist
+            rank = dist.get_rank()
+        if rank == 0:
+            torch.save(self.model.state_dict(), path)
+
+
+def _train_batch(store, trainer: RadarGNNTrainer, pos, window_size, augmentation, ransac):
+    """One batch of windows through the front-end and one training step: what train_sequence
+    and train_dataset do per batch.  Returns (flags or None, step_frames' result)."""
+    from . import frontend
+    flags = frontend.draw_flips(int(pos.shape[0])) if augmentation else None
+    win = store.windows(pos, window_size)
+    dd, gd = frontend.dynamic_frame(win, ransac, with_keys=True, flip=flags, numpy_mean=True)
+    return flags, trainer.step_frames(frontend.frame_batch(dd, gd))
+
+
+def _stack_rows(losses, accs, dev):
+    if not losses:
+        return (torch.empty((0, N_LOSS_SLOTS), dtype=torch.float32, device=dev),
+                torch.empty((0, 3), dtype=torch.float32, device=dev))
+    return torch.stack(losses), torch.stack(accs)
+
 
 def train_sequence(store, trainer: RadarGNNTrainer, cfg, indices, window_size: int = 10,
                    batch_windows: int = 64, augmentation: Optional[bool] = None, on_step=None):
@@ -1300,7 +1356,6 @@ def train_sequence(store, trainer: RadarGNNTrainer, cfg, indices, window_size: i
     ``on_step(step index, positions, flags or None, step_frames' result)`` is called after
     every batch.  Returns (losses f32 [steps, 4], accuracies f32 [steps, 3]) on the device, one
     row per batch that had a frame to train on (a skipped NaN step keeps its row)."""
-    from . import frontend
     if int(batch_windows) < 1:
         raise ValueError(f'batch_windows={batch_windows} < 1')
     idx = np.asarray(indices, dtype=np.int64).reshape(-1)
@@ -1309,20 +1364,121 @@ def train_sequence(store, trainer: RadarGNNTrainer, cfg, indices, window_size: i
     losses, accs = [], []
     for k, i0 in enumerate(range(0, int(idx.shape[0]), int(batch_windows))):
         pos = idx[i0:i0 + int(batch_windows)]
-        flags = frontend.draw_flips(int(pos.shape[0])) if augmentation else None
-        win = store.windows(pos, window_size)
-        dd, gd = frontend.dynamic_frame(win, ransac, with_keys=True, flip=flags, numpy_mean=True)
-        out = trainer.step_frames(frontend.frame_batch(dd, gd))
+        flags, out = _train_batch(store, trainer, pos, window_size, augmentation, ransac)
         if out is not None:
             losses.append(out[0])
             accs.append(out[1])
         if on_step is not None:
             on_step(k, pos, flags, out)
-    dev = trainer.engine.device
-    if not losses:
-        return (torch.empty((0, N_LOSS_SLOTS), dtype=torch.float32, device=dev),
-                torch.empty((0, 3), dtype=torch.float32, device=dev))
-    return torch.stack(losses), torch.stack(accs)
+    return _stack_rows(losses, accs, trainer.engine.device)
+
+
+def validate_sequence(store, trainer: RadarGNNTrainer, cfg, indices, window_size: int = 10,
+                      batch_windows: int = 64):
+    """The validation pass of train_model (training.py:110-125) over a ``SequenceStore`` or a
+    ``SequenceSet``: the windows ``indices`` in the given order (the validation loader does not
+    shuffle) in batches of ``batch_windows``, each ``store.windows`` ->
+    ``frontend.dynamic_frame`` (no flip; cfg.reject_static_meas_by_ransac passed on, offsets
+    to numpy's float32 track mean as in training) -> ``frontend.frame_batch`` ->
+    ``RadarGNNTrainer.validate_frames``.  A batch counts when its total loss -- the four
+    summed in order, ``sum(loss.values())`` -- is > 0 (:123), which leaves out 0, negatives
+    and NaN (``average_counted``).  Returns, all on the device and without a host read of its
+    own: (mean losses f64 [4], mean accuracies f64 [3], counted batches int64 [], losses f32
+    [batches, 4], accuracies f32 [batches, 3]); the rows are one per batch that had a frame,
+    the means NaN when no batch counts.  Weights, optimizer state and applied steps are
+    untouched."""
+    from . import frontend
+    if int(batch_windows) < 1:
+        raise ValueError(f'batch_windows={batch_windows} < 1')
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    ransac = bool(getattr(cfg, 'reject_static_meas_by_ransac', False))
+    losses, accs = [], []
+    for i0 in range(0, int(idx.shape[0]), int(batch_windows)):
+        win = store.windows(idx[i0:i0 + int(batch_windows)], window_size)
+        dd, gd = frontend.dynamic_frame(win, ransac, with_keys=True, numpy_mean=True)
+        out = trainer.validate_frames(frontend.frame_batch(dd, gd))
+        if out is not None:
+            losses.append(out[0])
+            accs.append(out[1])
+    lo, ac = _stack_rows(losses, accs, trainer.engine.device)
+    total = total_loss(lo)
+    mean_lo, n = average_counted(total, lo)
+    mean_ac, _ = average_counted(total, ac)
+    return mean_lo, mean_ac, n, lo, ac
+
+
+def total_loss(losses: torch.Tensor) -> torch.Tensor:
+    """``sum(loss.values())`` (training.py:77, :121) for rows of the four losses [..., 4]:
+    added in the dict's order, in float32."""
+    total = losses[..., 0]
+    for c in range(1, int(losses.shape[-1])):
+        total = total + losses[..., c]
+    return total
+
+
+def shuffled_batches(n: int, batch_size: int):
+    """``infinite_loader(DataLoader(dataset, batch_size, shuffle=True))``
+    (set_param_for_training_gnn.py:97-99, common.py:35-38) over the indices 0..n-1: an endless
+    generator of int64 index batches, a fresh permutation per epoch from torch's default
+    generator, every epoch's last batch short when batch_size does not divide n."""
+    from torch.utils.data import DataLoader
+    if int(n) < 1 or int(batch_size) < 1:
+        raise ValueError(f'n={n}, batch_size={batch_size}: both must be >= 1')
+    loader = DataLoader(range(int(n)), batch_size=int(batch_size), shuffle=True)
+    while True:
+        for batch in loader:
+            yield batch.numpy().astype(np.int64)
+
+
+def train_dataset(train_set, trainer: RadarGNNTrainer, cfg, val_set=None, train_indices=None,
+                  val_indices=None, max_iters: Optional[int] = None, iter_start_offset: int = 0,
+                  batch_windows: int = 8, val_period: int = 1000, weights_path=None,
+                  window_size: int = 10, on_step=None, on_validation=None):
+    """The iteration structure of train_model (training.py:66-134) over a training and a
+    validation ``SequenceSet`` (or ``SequenceStore``): for every iteration from
+    ``iter_start_offset`` to ``max_iters`` (default cfg.max_train_iter) one batch of
+    ``batch_windows`` windows from ``shuffled_batches`` over ``train_indices`` (default every
+    window of ``train_set``; e.g. ``sequence.dataset_indices``) goes through what
+    ``train_sequence`` does per batch (flip per cfg.dataset_augmentation); when
+    ``iter % val_period == 0`` or on the last iteration (:100) ``trainer.save(weights_path)``
+    runs if a path was given and ``validate_sequence`` over ``val_indices`` (default every
+    window of ``val_set``, in batches of ``batch_windows``) if a validation set was given.
+    ``on_step(iteration, windows, flags or None, step_frames' result)`` after every iteration,
+    ``on_validation(iteration, validate_sequence's result)`` after every validation.  Returns
+    (losses f32 [steps, 4], accuracies f32 [steps, 3], validations): the rows as
+    ``train_sequence`` returns them and one (iteration, mean losses, mean accuracies, counted
+    batches) per validation, the tensors on the device.  TensorBoard and console output are
+    the caller's (the two callbacks)."""
+    if int(batch_windows) < 1 or int(val_period) < 1:
+        raise ValueError(f'batch_windows={batch_windows}, val_period={val_period}: both >= 1')
+    max_iters = int(cfg.max_train_iter if max_iters is None else max_iters)
+    t_idx = np.arange(train_set.n_windows(window_size), dtype=np.int64) \
+        if train_indices is None else np.asarray(train_indices, dtype=np.int64).reshape(-1)
+    if val_set is not None:
+        v_idx = np.arange(val_set.n_windows(window_size), dtype=np.int64) \
+            if val_indices is None else np.asarray(val_indices, dtype=np.int64).reshape(-1)
+    augmentation = bool(cfg.dataset_augmentation)
+    ransac = bool(getattr(cfg, 'reject_static_meas_by_ransac', False))
+    losses, accs, validations = [], [], []
+    batches = shuffled_batches(int(t_idx.shape[0]), batch_windows) \
+        if iter_start_offset < max_iters else None
+    for it in range(int(iter_start_offset), max_iters):
+        pos = t_idx[next(batches)]
+        flags, out = _train_batch(train_set, trainer, pos, window_size, augmentation, ransac)
+        if out is not None:
+            losses.append(out[0])
+            accs.append(out[1])
+        if on_step is not None:
+            on_step(it, pos, flags, out)
+        if it % int(val_period) == 0 or it == max_iters - 1:
+            if weights_path is not None:
+                trainer.save(weights_path)
+            if val_set is not None:
+                res = validate_sequence(val_set, trainer, cfg, v_idx, window_size, batch_windows)
+                validations.append((it,) + res[:3])
+                if on_validation is not None:
+                    on_validation(it, res)
+    return _stack_rows(losses, accs, trainer.engine.device) + (validations,)
 
 
 # ------------------------------------------------------------------ object-head finetuning
@@ -1495,7 +1651,22 @@ def average_counted(losses, values=None):
     """finetuning.py:86-101's rule for what the validation trackers average: an iteration
     counts when its loss is > 0 (``if loss > 0:``), which leaves out 0, negatives and NaN.
     Returns (mean of ``values`` -- default the losses themselves -- over the iterations that
-    count, their number); (nan, 0) when none counts.  Host only."""
+    count, their number); (nan, 0) when none counts.  Host values give host numbers.
+
+    ``losses`` a torch tensor [n] (train_model's validation trackers, training.py:123-125,
+    follow the same rule): the same on the tensor's device with no host read -- ``values`` a
+    tensor [n] or [n, k] averaged per column in float64; returns (mean f64 [] or [k], count
+    int64 [])."""
+    if isinstance(losses, torch.Tensor):
+        lo = losses.reshape(-1)
+        va = (lo if values is None else values).to(torch.float64)
+        if int(va.shape[0]) != int(lo.shape[0]):
+            raise ValueError(f'{int(va.shape[0])} values for {int(lo.shape[0])} losses')
+        keep = lo > 0
+        n = keep.sum()
+        k = keep.reshape((-1,) + (1,) * (va.dim() - 1))
+        # 0 / 0 = nan when none counts; a value that does not count is never added
+        return torch.where(k, va, torch.zeros_like(va)).sum(dim=0) / n, n
     lo = np.asarray(losses, dtype=np.float64).reshape(-1)
     va = lo if values is None else np.asarray(values, dtype=np.float64).reshape(-1)
     if va.shape != lo.shape:

@@ -934,6 +934,22 @@ typedef struct rg_window_batch {
 int rg_sequence_windows(const rg_sequence* seq, const int* win_first, int n_windows, int W,
                         long capacity, const rg_window_batch* out, void* stream);
 
+/* The windows of a batch cut from several sequences (sequence.py, SequenceSet): window b is
+ * W consecutive scenes of sequence win[2b] starting at scene win[2b+1].  seqs is a DEVICE
+ * array of n_seq rg_sequence descriptors (8-byte aligned), win a device int32 [n_windows][2].
+ * The outputs, the two launches and every clamp are rg_sequence_windows': each descriptor's
+ * tables are read as that entry point reads its one sequence's, src_row is the row inside
+ * the window's own sequence, and the non-zero track keys of window b become
+ * k + b * key_stride (key_stride >= the largest n_tracks keeps the windows' keys apart).  A
+ * sequence id outside [0, n_seq) makes the window's scans empty with NaN poses; nothing is
+ * read for it.  The descriptors' own sizes and pointers lie on the device and are not
+ * validated on the host: a size <= 0 makes that table empty.  RG_ERR_ARG, launching
+ * nothing: a NULL pointer, n_seq < 1, key_stride < 0, W < 1, a negative n_windows or
+ * capacity, n_windows * W or n_windows * key_stride beyond int32. */
+int rg_sequence_set_windows(const rg_sequence* seqs, int n_seq, int key_stride, const int* win,
+                            int n_windows, int W, long capacity, const rg_window_batch* out,
+                            void* stream);
+
 /* ------------------------------------------------------------ training feed */
 
 /* The x-axis flip augmentation of get_data_for_datagen (read_data.py:522-524) for a batch of
