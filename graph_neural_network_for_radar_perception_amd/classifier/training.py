@@ -31,7 +31,9 @@ The loop (``train_model``, training.py:48-135): ``ClassifierTrainer`` is one ite
 the fused optimizer (NaN skip and MultiStepLR on the device, one all-reduce bucket),
 ``train_classifier_sequence`` feeds it from a ``SequenceStore`` through the detector's
 proposals (``datagen_classifier.py:195-308``) and ``validate_classifier_sequence`` is the
-validation pass.
+validation pass.  ``train_model_accumulate_grad`` (training.py:138-236) is
+``grad_accumulation_steps`` of that loop: ``accumulate_objects`` / ``accumulate_inputs`` per
+micro-batch and one ``apply_accumulated`` per outer iteration (``training.GradAccumulator``).
 """
 from __future__ import annotations
 
@@ -492,6 +494,7 @@ class ClassifierTrainer:
         dt.broadcast_parameters(self.opt.flat, world)
         model_training.invalidate_plans()
         self.one = torch.ones(1, dtype=torch.float32, device=self.opt.flat.device)
+        self.accum = dt.GradAccumulator(self.opt, N_LOSS_SLOTS)
 
     @property
     def engine(self) -> ClassifierTrainEngine:
@@ -532,6 +535,49 @@ class ClassifierTrainer:
         begin, end = inp.ranges()
         return self.step_objects(inp.object_features, inp.object_num_meas, begin, end,
                                  inp.object_class, inp.n_rows, inp.n_edges, inp.max_size)
+
+    # -------- gradient accumulation (train_model_accumulate_grad, training.py:138-236)
+    def accumulate_objects(self, node_features, object_size, begin, end, labels, n_nodes: int,
+                           n_edges: int, max_size: int, n_accum: int) -> torch.Tensor:
+        """The micro-batch twin of ``step_objects``: one of up to ``n_accum`` micro-batches of
+        an outer iteration.  Forward with tape, backward of ``loss / n_accum``
+        (``training.GradAccumulator.g``), and the micro-batch's complete gradient and scaled
+        loss are added to the accumulator; no all-reduce, no optimizer launch, no weight and no
+        packed image changes until ``apply_accumulated``.  Returns the unscaled loss f32 [1].
+        ValueError for ``n_accum < 1`` or one that differs from the open accumulation's."""
+        self.accum.open(n_accum)
+        eng = self.engine
+        loss, tape = eng.forward_objects(node_features, object_size, begin, end, labels,
+                                         int(n_nodes), int(n_edges), int(max_size))
+        eng.backward(tape, self.accum.g(n_accum))
+        self.accum.add(eng, loss)
+        return loss
+
+    def accumulate_inputs(self, inp, n_accum: int):
+        """``accumulate_objects`` from an objects.ClassifierInputs made with node_labels.  A
+        batch without a kept object, or ``inp`` None (a batch without a frame), contributes
+        nothing -- the divisor stays ``n_accum`` (training.py:163, ``if batch_data != None``)
+        -- and None is returned; it still opens the accumulation, so the apply that follows is
+        the outer iteration's."""
+        self.accum.open(n_accum)
+        if inp is None or inp.n_objects == 0:
+            return None
+        if inp.object_class is None:
+            raise ValueError('accumulate_inputs needs ClassifierInputs made with node_labels')
+        begin, end = inp.ranges()
+        return self.accumulate_objects(inp.object_features, inp.object_num_meas, begin, end,
+                                       inp.object_class, inp.n_rows, inp.n_edges, inp.max_size,
+                                       n_accum)
+
+    def apply_accumulated(self) -> int:
+        """Close the outer iteration: ONE gradient all-reduce and ONE optimizer launch from the
+        accumulated micro-batches -- at most one applied step and one scheduler step.  A NaN
+        loss in any micro-batch (on any rank) skips the update.  Returns the number of
+        micro-batches that contributed; with none, ``world == 1`` launches nothing (not even
+        the train engine's first packing) and ``world > 1`` joins the all-reduce with zero
+        gradients and a NaN slot so that every rank skips (``training.GradAccumulator``).
+        RuntimeError without an open accumulation."""
+        return self.accum.apply(self.world)
 
     def save(self, path):
         """save_model_weights (training.py:15-17) on rank 0: the reference's state_dict keys."""
@@ -577,7 +623,8 @@ def _batches(indices, batch_windows):
 def train_classifier_sequence(store, detector, trainer: ClassifierTrainer, cfg, indices,
                               window_size: int = 10, batch_windows: int = 64,
                               augmentation: Optional[bool] = None, min_meas: int = 2,
-                              meas_noise_cov=None, on_step=None) -> torch.Tensor:
+                              meas_noise_cov=None, on_step=None,
+                              grad_accumulation_steps: int = 1) -> torch.Tensor:
     """Classifier training from a ``sequence.SequenceStore``: the sliding positions ``indices``,
     in the caller's order, in batches of ``batch_windows``; each batch goes ``store.windows`` ->
     ``frontend.dynamic_frame`` (with the x-axis flip when ``augmentation``, default
@@ -592,22 +639,39 @@ def train_classifier_sequence(store, detector, trainer: ClassifierTrainer, cfg, 
     ``on_step(step index, positions, flags or None, loss or None, inputs)`` is called after
     every batch (inputs None for a batch without a frame; step_inputs is called for it too, so
     a rank of several still joins the step's all-reduce).  Returns the losses f32 [steps] on
-    the device: one entry per batch that had an object (a skipped NaN step keeps its entry)."""
+    the device: one entry per batch that had an object (a skipped NaN step keeps its entry).
+
+    ``grad_accumulation_steps`` = K > 1 (train_model_accumulate_grad, training.py:138-236):
+    consecutive groups of K batches form one outer iteration -- each batch a micro-batch through
+    ``ClassifierTrainer.accumulate_inputs``, then one ``apply_accumulated``; a trailing group
+    shorter than K is applied with what it has, the divisor staying K.  Flags are drawn per
+    micro-batch; ``on_step`` is called after every micro-batch with the OUTER iteration first
+    (for a group's last micro-batch after the apply, as with K = 1); the entries are one per
+    contributing micro-batch, unscaled.  All K micro-batches always run: a NaN loss skips the
+    step at the apply, where the reference breaks out of the group.  K = 1 is the path above,
+    unchanged."""
     from .. import frontend
+    K = dt.accumulation_steps(grad_accumulation_steps)
     augmentation = bool(cfg.dataset_augmentation if augmentation is None else augmentation)
     cache: dict = {}
     losses = []
-    for k, pos in _batches(indices, batch_windows):
+    batches = list(_batches(indices, batch_windows))
+    for k, pos in batches:
         flags = frontend.draw_flips(int(pos.shape[0])) if augmentation else None
         inp = _sequence_inputs(store, detector, cfg, pos, window_size, flags, min_meas,
                                meas_noise_cov, cache)
         # (a batch without a frame goes to the trainer too: with world > 1 the rank must join
         # the step's all-reduce, or its peers wait for it)
-        loss = trainer.step_inputs(inp)
+        if K == 1:
+            loss = trainer.step_inputs(inp)
+        else:
+            loss = trainer.accumulate_inputs(inp, K)
+            if (k + 1) % K == 0 or k + 1 == len(batches):
+                trainer.apply_accumulated()
         if loss is not None:
             losses.append(loss)
         if on_step is not None:
-            on_step(k, pos, flags, loss, inp)
+            on_step(k // K, pos, flags, loss, inp)
     if not losses:
         return torch.empty(0, dtype=torch.float32, device=trainer.opt.flat.device)
     return torch.cat(losses)

@@ -28,7 +28,10 @@ The loop around the step (training.py:66-134): train_sequence feeds step_frames 
 SequenceStore or a SequenceSet in the caller's order; train_dataset is train_model's iteration
 structure over a training and a validation set -- shuffled_batches (the endless shuffling
 loader), validate_frames / validate_sequence (the no-grad validation pass) and
-RadarGNNTrainer.save every val_period iterations.
+RadarGNNTrainer.save every val_period iterations.  train_model_accumulate_grad
+(training.py:189-333) is grad_accumulation_steps of both loops: GradAccumulator sums the
+micro-batches' gradients as autograd does and applies one all-reduce and one optimizer step per
+outer iteration (RadarGNNTrainer.accumulate / accumulate_frames / apply_accumulated).
 
 Object-head finetuning (gnn/finetuning.py, set_param_for_finetuning_obj_classifier.py) trains
 predict_class alone on a frozen backbone: HeadTrainEngine tapes the head from the no-grad
@@ -1141,6 +1144,100 @@ def broadcast_parameters(flat: torch.Tensor, world: int, src: int = 0):
         dist.broadcast(flat, src)
 
 
+# ------------------------------------------------------------------ gradient accumulation
+class GradAccumulator:
+    """One optimizer step from up to ``n_accum`` micro-batches (train_model_accumulate_grad,
+    gnn/training.py:189-333 and classifier/training.py:138-236: ``(loss / K).backward()`` per
+    micro-batch, one ``optimizer.step()`` per K).  Owns a second bucket laid out like the
+    engine's ``flat_bucket`` -- the parameters' gradients, then ``n_loss_slots`` loss slots.
+
+    Per contributing micro-batch the trainer runs the engine's backward with ``zero_grads=True``
+    and the upstream gradient ``g(n_accum)`` = ones / K (torch's own division, the value
+    autograd hands a loss that was divided by K), then ``add``: the losses times g go to the
+    engine's loss slots and the whole engine bucket is added to this one in float32, in
+    micro-batch order (the first one is copied) -- autograd's AccumulateGrad, so the
+    accumulated gradient is bit-identical to ``p.grad`` after K ``(total / K).backward()``
+    calls.  ``apply`` makes ONE ``allreduce_gradients`` of the bucket and ONE optimizer launch;
+    the slots' sum is NaN exactly when some micro-batch's scaled total is (the losses are
+    non-negative, so no infinities cancel), and the optimizer kernel then skips the update on
+    every rank (the reference's ``skip`` flag, training.py:210, 225-231).
+
+    An empty micro-batch (``open`` alone) contributes nothing and the divisor stays K.  When
+    no micro-batch contributed: ``world == 1`` launches nothing and counts no step;
+    ``world > 1`` sends zero gradients and NaN slots into the one all-reduce, so every rank
+    skips (as ``step_frames`` / ``step_inputs`` do for an empty batch).
+
+    Unlike the reference, which breaks out of the K batches at the first NaN loss, nothing is
+    read back per micro-batch: all K run and the step is skipped at the apply.  Weights,
+    optimizer state and the applied-step count are the reference's; the data order after a NaN
+    batch is not."""
+
+    def __init__(self, opt, n_loss_slots: int):
+        self.opt = opt
+        self.n_loss_slots = int(n_loss_slots)
+        self.n_accum: Optional[int] = None     # K of the open accumulation; None: none open
+        self.count = 0                         # micro-batches that contributed to it
+        self.bucket = self.grad = self.slots = None    # made at the first open
+        self._g = (0, None)                    # (K, ones / K)
+
+    def open(self, n_accum: int):
+        """Begin an accumulation over n_accum micro-batches, or continue the open one."""
+        k = int(n_accum)
+        if k < 1:
+            raise ValueError(f'n_accum={n_accum} < 1')
+        if self.n_accum is not None and k != self.n_accum:
+            raise ValueError(f'n_accum changed from {self.n_accum} to {k} inside an open '
+                             'accumulation (apply_accumulated() closes it)')
+        if self.bucket is None:
+            flat = self.opt.flat
+            n = int(flat.numel())
+            self.bucket = torch.zeros(n + self.n_loss_slots, dtype=torch.float32,
+                                      device=flat.device)
+            self.grad, self.slots = self.bucket[:n], self.bucket[n:]
+        if self.n_accum is None:
+            self.n_accum, self.count = k, 0
+
+    def g(self, n_accum: int) -> torch.Tensor:
+        """ones / K, f32 [n_loss_slots] on the device, made once per K."""
+        k = int(n_accum)
+        if self._g[0] != k:
+            ones = torch.ones(self.n_loss_slots, dtype=torch.float32, device=self.opt.flat.device)
+            self._g = (k, ones / k)
+        return self._g[1]
+
+    def add(self, engine_, losses: torch.Tensor):
+        """The open accumulation += the micro-batch whose complete gradient (backward with
+        g(n_accum), zero_grads=True) is in engine_.flat_grad and whose unscaled losses are
+        ``losses``."""
+        if self.n_accum is None:
+            raise RuntimeError('add() without an open accumulation')
+        if engine_.flat_bucket.numel() != self.bucket.numel():
+            raise ValueError(f'the engine\'s bucket has {engine_.flat_bucket.numel()} entries, '
+                             f'the accumulator\'s {self.bucket.numel()}')
+        torch.mul(losses.reshape(-1), self.g(self.n_accum), out=engine_.loss_slots)
+        if self.count == 0:
+            self.bucket.copy_(engine_.flat_bucket)
+        else:
+            self.bucket.add_(engine_.flat_bucket)
+        self.count += 1
+
+    def apply(self, world: int = 1) -> int:
+        """Close the accumulation: one all-reduce over ``world`` ranks, one optimizer launch.
+        Returns the number of micro-batches that contributed (0: see the class)."""
+        if self.n_accum is None:
+            raise RuntimeError('apply_accumulated() without an open accumulation')
+        n = self.count
+        self.n_accum, self.count = None, 0
+        if n == 0:
+            if world <= 1:
+                return 0
+            self.grad.zero_()
+            self.slots.fill_(float('nan'))
+        scale = allreduce_gradients(self.bucket, world)
+        self.opt.step(self.grad, grad_scale=scale, losses=self.slots)
+        return n
+
+
 # ------------------------------------------------------------------ labels on the device
 def training_labels(batch, gb, cfg, ws_cache: Optional[dict] = None) -> dict:
     """The labels of RadarScenesDataset.__getitem__ (datagen_gnn.py:126-139) for a batch of
@@ -1217,6 +1314,20 @@ class RadarGNNTrainer:
         self.engine = model_training.train_engine()
         self.ones = torch.ones(4, dtype=torch.float32, device=self.engine.device)
         self.ws_cache: dict = {}
+        self.accum = GradAccumulator(self.opt, N_LOSS_SLOTS)
+
+    def _frame_inputs(self, batch):
+        """Graph build, training_labels and the ONE device-to-host copy of the three host sizes
+        (edges, pairs, clusters) for a non-empty frame_batch: (GraphBatch, its graph, labels,
+        cluster count)."""
+        from .graph_features import build_graph_batch
+        gb = build_graph_batch(batch, self.cfg, ws_cache=self.ws_cache)
+        g = gb.graph
+        labels = training_labels(batch, gb, self.cfg, self.ws_cache)
+        sizes = torch.cat((gb.n_edges_dev.reshape(1), g.n_pairs_dev.reshape(1),
+                           labels['n_clusters_dev'].reshape(1))).tolist()
+        g.n_edges, g.n_pairs, ncl = (int(v) for v in sizes)
+        return gb, g, labels, ncl
 
     def step(self, batch, labels: dict, events=None):
         from .graph_features import build_graph_batch
@@ -1257,7 +1368,6 @@ class RadarGNNTrainer:
         the gradient all-reduce, with zero gradients and NaN in its loss slots: the summed
         loss is NaN on every rank, so the optimizer kernel skips the step everywhere
         (skip_batch) and no rank waits for a missing peer; None is returned."""
-        from .graph_features import build_graph_batch
         eng = self.engine
         if batch.n_frames == 0:
             if self.world > 1:
@@ -1266,12 +1376,7 @@ class RadarGNNTrainer:
                 scale = allreduce_gradients(eng.flat_bucket, self.world)
                 self.opt.step(eng.flat_grad, grad_scale=scale, losses=eng.loss_slots)
             return None
-        gb = build_graph_batch(batch, self.cfg, ws_cache=self.ws_cache)
-        g = gb.graph
-        labels = training_labels(batch, gb, self.cfg, self.ws_cache)
-        sizes = torch.cat((gb.n_edges_dev.reshape(1), g.n_pairs_dev.reshape(1),
-                           labels['n_clusters_dev'].reshape(1))).tolist()
-        g.n_edges, g.n_pairs, ncl = (int(v) for v in sizes)
+        gb, g, labels, ncl = self._frame_inputs(batch)
 
         def mark(name):
             if events is not None:
@@ -1291,6 +1396,54 @@ class RadarGNNTrainer:
         self.opt.step(eng.flat_grad, grad_scale=scale, losses=eng.loss_slots)
         return losses, acc, gb
 
+    # -------- gradient accumulation (train_model_accumulate_grad, training.py:189-333)
+    def accumulate(self, batch, labels: dict, n_accum: int):
+        """The micro-batch twin of ``step``: one of up to ``n_accum`` micro-batches of an outer
+        iteration.  Forward with tape, backward of ``loss / n_accum`` (``GradAccumulator.g``),
+        and the micro-batch's complete gradient and scaled losses are added to the
+        accumulator; no all-reduce, no optimizer launch, no weight and no packed image changes
+        until ``apply_accumulated``.  Returns what ``step`` does, the losses unscaled.
+        ValueError for ``n_accum < 1`` or one that differs from the open accumulation's."""
+        from .graph_features import build_graph_batch
+        self.accum.open(n_accum)
+        gb = build_graph_batch(batch, self.cfg, ws_cache=self.ws_cache)
+        g = gb.graph
+        g.n_edges = int(gb.n_edges_dev.item())
+        g.n_pairs = int(g.n_pairs_dev.item())
+        losses, acc, tape = self.engine.forward(gb.node_features, gb.edge_features, g,
+                                                batch.cluster_ptr, batch.cluster_idx,
+                                                batch.n_clusters, labels)
+        self.engine.backward(tape, self.accum.g(n_accum))
+        self.accum.add(self.engine, losses)
+        return losses, acc, gb
+
+    def accumulate_frames(self, batch, n_accum: int):
+        """The micro-batch twin of ``step_frames`` (``accumulate`` for a
+        ``frontend.frame_batch(dd, gd)`` batch made ``with_keys=True``).  An empty batch
+        contributes nothing -- the divisor stays ``n_accum`` (training.py:215, ``if
+        graph_features != None``) -- and None is returned; it still opens the accumulation,
+        so the apply that follows is the outer iteration's."""
+        self.accum.open(n_accum)
+        if batch.n_frames == 0:
+            return None
+        eng = self.engine
+        gb, g, labels, ncl = self._frame_inputs(batch)
+        losses, acc, tape = eng.forward(gb.node_features, gb.edge_features, g,
+                                        labels['cluster_ptr'], labels['cluster_idx'], ncl, labels)
+        eng.backward(tape, self.accum.g(n_accum))
+        self.accum.add(eng, losses)
+        return losses, acc, gb
+
+    def apply_accumulated(self) -> int:
+        """Close the outer iteration: ONE gradient all-reduce and ONE optimizer launch from the
+        accumulated micro-batches -- at most one applied step and one scheduler step, so
+        ``applied_steps()`` and the milestones count outer iterations.  A NaN loss in any
+        micro-batch (on any rank) skips the update.  Returns the number of micro-batches that
+        contributed; with none, ``world == 1`` launches nothing and ``world > 1`` joins the
+        all-reduce with zero gradients and NaN slots so that every rank skips
+        (``GradAccumulator``).  RuntimeError without an open accumulation."""
+        return self.accum.apply(self.world)
+
     def validate_frames(self, batch):
         """The validation forward of train_model (training.py:111-121) for a
         ``frontend.frame_batch(dd, gd)`` batch made ``with_keys=True``: ``step_frames`` up to
@@ -1299,16 +1452,10 @@ class RadarGNNTrainer:
         f32 [3]) equal ``step_frames``' bit for bit -- and nothing after it: no backward, no
         all-reduce, no optimizer launch; the tape is dropped.  One device-to-host copy (the
         three sizes).  None for an empty batch, on every rank (nothing to join)."""
-        from .graph_features import build_graph_batch
         if batch.n_frames == 0:
             return None
         with torch.no_grad():
-            gb = build_graph_batch(batch, self.cfg, ws_cache=self.ws_cache)
-            g = gb.graph
-            labels = training_labels(batch, gb, self.cfg, self.ws_cache)
-            sizes = torch.cat((gb.n_edges_dev.reshape(1), g.n_pairs_dev.reshape(1),
-                               labels['n_clusters_dev'].reshape(1))).tolist()
-            g.n_edges, g.n_pairs, ncl = (int(v) for v in sizes)
+            gb, g, labels, ncl = self._frame_inputs(batch)
             losses, acc, _ = self.engine.forward(gb.node_features, gb.edge_features, g,
                                                  labels['cluster_ptr'], labels['cluster_idx'],
                                                  ncl, labels)
@@ -1325,14 +1472,27 @@ class RadarGNNTrainer:
             torch.save(self.model.state_dict(), path)
 
 
-def _train_batch(store, trainer: RadarGNNTrainer, pos, window_size, augmentation, ransac):
+def _train_batch(store, trainer: RadarGNNTrainer, pos, window_size, augmentation, ransac,
+                 n_accum: Optional[int] = None):
     """One batch of windows through the front-end and one training step: what train_sequence
-    and train_dataset do per batch.  Returns (flags or None, step_frames' result)."""
+    and train_dataset do per batch.  n_accum: the batch is a micro-batch of an accumulation
+    over n_accum (accumulate_frames instead of step_frames).  Returns (flags or None,
+    step_frames' result)."""
     from . import frontend
     flags = frontend.draw_flips(int(pos.shape[0])) if augmentation else None
     win = store.windows(pos, window_size)
     dd, gd = frontend.dynamic_frame(win, ransac, with_keys=True, flip=flags, numpy_mean=True)
-    return flags, trainer.step_frames(frontend.frame_batch(dd, gd))
+    fb = frontend.frame_batch(dd, gd)
+    if n_accum is None:
+        return flags, trainer.step_frames(fb)
+    return flags, trainer.accumulate_frames(fb, n_accum)
+
+
+def accumulation_steps(grad_accumulation_steps) -> int:
+    k = int(grad_accumulation_steps)
+    if k < 1:
+        raise ValueError(f'grad_accumulation_steps={grad_accumulation_steps} < 1')
+    return k
 
 
 def _stack_rows(losses, accs, dev):
@@ -1343,7 +1503,8 @@ def _stack_rows(losses, accs, dev):
 
 
 def train_sequence(store, trainer: RadarGNNTrainer, cfg, indices, window_size: int = 10,
-                   batch_windows: int = 64, augmentation: Optional[bool] = None, on_step=None):
+                   batch_windows: int = 64, augmentation: Optional[bool] = None, on_step=None,
+                   grad_accumulation_steps: int = 1):
     """Training from a ``sequence.SequenceStore``: the sliding positions ``indices``, in the
     caller's order (shuffling is the caller's), in batches of ``batch_windows``; each batch
     goes ``store.windows`` -> ``frontend.dynamic_frame`` (with the x-axis flip when
@@ -1355,21 +1516,36 @@ def train_sequence(store, trainer: RadarGNNTrainer, cfg, indices, window_size: i
     ``select_dynamic`` (and the RANSAC draws), ``frame_batch`` and ``step_frames`` do.
     ``on_step(step index, positions, flags or None, step_frames' result)`` is called after
     every batch.  Returns (losses f32 [steps, 4], accuracies f32 [steps, 3]) on the device, one
-    row per batch that had a frame to train on (a skipped NaN step keeps its row)."""
+    row per batch that had a frame to train on (a skipped NaN step keeps its row).
+
+    ``grad_accumulation_steps`` = K > 1 (train_model_accumulate_grad, training.py:189-333):
+    consecutive groups of K batches form one outer iteration -- each batch a micro-batch through
+    ``RadarGNNTrainer.accumulate_frames``, then one ``apply_accumulated`` (one all-reduce, one
+    optimizer and scheduler step); a trailing group shorter than K is applied with what it has,
+    the divisor staying K.  Flags are drawn per micro-batch; ``on_step`` is called after every
+    micro-batch with the OUTER iteration as its first argument (for a group's last micro-batch
+    after the apply, as with K = 1); the rows are one per contributing micro-batch, unscaled.
+    All K micro-batches always run: a NaN loss skips the step at the apply, where the reference
+    breaks out of the group (``GradAccumulator``).  K = 1 is the path above, unchanged."""
     if int(batch_windows) < 1:
         raise ValueError(f'batch_windows={batch_windows} < 1')
+    K = accumulation_steps(grad_accumulation_steps)
     idx = np.asarray(indices, dtype=np.int64).reshape(-1)
     augmentation = bool(cfg.dataset_augmentation if augmentation is None else augmentation)
     ransac = bool(getattr(cfg, 'reject_static_meas_by_ransac', False))
     losses, accs = [], []
-    for k, i0 in enumerate(range(0, int(idx.shape[0]), int(batch_windows))):
+    starts = range(0, int(idx.shape[0]), int(batch_windows))
+    for k, i0 in enumerate(starts):
         pos = idx[i0:i0 + int(batch_windows)]
-        flags, out = _train_batch(store, trainer, pos, window_size, augmentation, ransac)
+        flags, out = _train_batch(store, trainer, pos, window_size, augmentation, ransac,
+                                  K if K > 1 else None)
+        if K > 1 and ((k + 1) % K == 0 or k + 1 == len(starts)):
+            trainer.apply_accumulated()
         if out is not None:
             losses.append(out[0])
             accs.append(out[1])
         if on_step is not None:
-            on_step(k, pos, flags, out)
+            on_step(k // K, pos, flags, out)
     return _stack_rows(losses, accs, trainer.engine.device)
 
 
@@ -1433,7 +1609,8 @@ def shuffled_batches(n: int, batch_size: int):
 def train_dataset(train_set, trainer: RadarGNNTrainer, cfg, val_set=None, train_indices=None,
                   val_indices=None, max_iters: Optional[int] = None, iter_start_offset: int = 0,
                   batch_windows: int = 8, val_period: int = 1000, weights_path=None,
-                  window_size: int = 10, on_step=None, on_validation=None):
+                  window_size: int = 10, on_step=None, on_validation=None,
+                  grad_accumulation_steps: int = 1):
     """The iteration structure of train_model (training.py:66-134) over a training and a
     validation ``SequenceSet`` (or ``SequenceStore``): for every iteration from
     ``iter_start_offset`` to ``max_iters`` (default cfg.max_train_iter) one batch of
@@ -1448,9 +1625,19 @@ def train_dataset(train_set, trainer: RadarGNNTrainer, cfg, val_set=None, train_
     (losses f32 [steps, 4], accuracies f32 [steps, 3], validations): the rows as
     ``train_sequence`` returns them and one (iteration, mean losses, mean accuracies, counted
     batches) per validation, the tensors on the device.  TensorBoard and console output are
-    the caller's (the two callbacks)."""
+    the caller's (the two callbacks).
+
+    ``grad_accumulation_steps`` = K > 1 (train_model_accumulate_grad, training.py:189-333):
+    every iteration draws K batches from ``shuffled_batches``, each a micro-batch through
+    ``accumulate_frames``, then one ``apply_accumulated``; ``max_iters``, ``val_period``, the
+    save and the validation count these OUTER iterations (:248).  ``on_step`` is called after
+    every micro-batch with the outer iteration first (the K-th one after the apply); the rows
+    are one per contributing micro-batch, unscaled.  All K always run (``GradAccumulator``: a
+    NaN loss skips the step at the apply instead of breaking out of the group).  K = 1 is the
+    path above, unchanged."""
     if int(batch_windows) < 1 or int(val_period) < 1:
         raise ValueError(f'batch_windows={batch_windows}, val_period={val_period}: both >= 1')
+    K = accumulation_steps(grad_accumulation_steps)
     max_iters = int(cfg.max_train_iter if max_iters is None else max_iters)
     t_idx = np.arange(train_set.n_windows(window_size), dtype=np.int64) \
         if train_indices is None else np.asarray(train_indices, dtype=np.int64).reshape(-1)
@@ -1463,13 +1650,17 @@ def train_dataset(train_set, trainer: RadarGNNTrainer, cfg, val_set=None, train_
     batches = shuffled_batches(int(t_idx.shape[0]), batch_windows) \
         if iter_start_offset < max_iters else None
     for it in range(int(iter_start_offset), max_iters):
-        pos = t_idx[next(batches)]
-        flags, out = _train_batch(train_set, trainer, pos, window_size, augmentation, ransac)
-        if out is not None:
-            losses.append(out[0])
-            accs.append(out[1])
-        if on_step is not None:
-            on_step(it, pos, flags, out)
+        for j in range(K):
+            pos = t_idx[next(batches)]
+            flags, out = _train_batch(train_set, trainer, pos, window_size, augmentation, ransac,
+                                      K if K > 1 else None)
+            if K > 1 and j == K - 1:
+                trainer.apply_accumulated()
+            if out is not None:
+                losses.append(out[0])
+                accs.append(out[1])
+            if on_step is not None:
+                on_step(it, pos, flags, out)
         if it % int(val_period) == 0 or it == max_iters - 1:
             if weights_path is not None:
                 trainer.save(weights_path)
