@@ -157,6 +157,9 @@ _SIGNATURES = {
     'rg_eval_associate_workspace_size': (_S, [_I, _I]),
     'rg_eval_associate': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P,
                                _P, _P, _P, _P, _P, _P, _P, _S, _P]),
+    'rg_eval_associate_l2_workspace_size': (_S, [_I, _I]),
+    'rg_eval_associate_l2': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P,
+                                  _P, _P, _P, _P, _P, _P, _P, _P, _S, _P]),
     'rg_eval_accumulate': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     'rg_eval_node_confusion': (_I, [_P, _I, _P, _L, _I, _P, _P, _P, _P]),
     # object stage (objects.hip)

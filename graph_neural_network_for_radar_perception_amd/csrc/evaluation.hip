@@ -14,6 +14,9 @@
 //                           pairs, sorted by (frame, d, gt, pred) and walked greedily by one
 //                           wave per frame; the remaining picks pair the unused rows and
 //                           columns in ascending order at d = 1.0f;
+//   rg_eval_associate_l2  : the same function with the 'l2_norm' criterion: the dense matrix
+//                           of centre distances, recomputed from the centres by one workgroup
+//                           per frame and never stored (see l2_assoc_kernel);
 //   rg_eval_accumulate    : the notebook's confusion / gt_count / pred_count updates;
 //   rg_eval_node_confusion: the segmentation notebook's node-level confusion matrix.
 // The accumulators are int64: integer adds make them independent of the arrival order.  Each
@@ -330,6 +333,188 @@ __global__ __launch_bounds__(WAVE) void walk_kernel(
   if (lane == 0) pk.count[f] = m;
 }
 
+// ------------------------------------------------------------------ l2_norm association
+
+// The 'l2_norm' criterion: dist[g][p] = float32 Euclidean distance between the centres of the
+// frame's kept clusters, a dense G x P matrix that is never stored.  One workgroup per frame;
+// every row caches the minimum of its unused columns (d, column; lowest column on ties), a
+// round takes the workgroup-wide minimum of (d, row) over the unused rows, and only the rows
+// whose cached column was just taken are rescanned (one wave per row, 64 columns a step).
+// G P distances up front, P per rescanned row: O(min(G, P) G P) when every row keeps wanting
+// the same column (co-located centres).  Every loop is bounded by G, P and min(G, P).
+static constexpr int L2_THREADS = 512;
+static constexpr int L2_WAVES = L2_THREADS / WAVE;
+// kept clusters a side of a frame whose state is held in LDS; a larger frame keeps the same
+// state in the workspace
+static constexpr int L2_LDS_CAP = 4096;
+static constexpr int L2_SLOT_BYTES = 2 * 8 + 3 * 4 + 2;  // per cluster of the larger side
+
+struct L2State {
+  float2* cen_g;         // [G] centres of the kept ground-truth clusters (rows)
+  float2* cen_p;         // [P] centres of the kept predicted clusters (columns)
+  float* best_d;         // [G] minimum of the row over the unused columns
+  int* best_c;           // [G] its column
+  int* inv;              // [G] rows to rescan
+  unsigned char* rused;  // [G]
+  unsigned char* cused;  // [P]
+};
+
+__device__ __forceinline__ u64 wave_min_u64(u64 k) {
+#pragma unroll
+  for (int o = WAVE / 2; o > 0; o >>= 1) {
+    const u64 t = __shfl_xor(k, o);
+    k = t < k ? t : k;
+  }
+  return k;
+}
+
+__device__ __forceinline__ bool finite_f32(float v) {
+  return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u;
+}
+
+// the picks of one frame (G, P >= 1); wkey [L2_WAVES] and n_inv are LDS
+__device__ __forceinline__ void l2_frame(const L2State s, int f, int G, int P, int bg, int bp,
+                                         const int* __restrict__ klist_g,
+                                         const int* __restrict__ klist_p,
+                                         const float* __restrict__ gt_mu,
+                                         const float* __restrict__ pred_mu, float eps, Picks pk,
+                                         int* bad_value, u64* wkey, int* n_inv) {
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const int m = G < P ? G : P;
+  int bad = 0;
+  for (int r = tid; r < G; r += L2_THREADS) {
+    const int c = klist_g[bg + r];
+    const float2 v = make_float2(gt_mu[2 * (size_t)c], gt_mu[2 * (size_t)c + 1]);
+    bad |= !(finite_f32(v.x) && finite_f32(v.y));
+    s.cen_g[r] = v;
+    s.rused[r] = 0;
+    s.inv[r] = r;
+  }
+  for (int c = tid; c < P; c += L2_THREADS) {
+    const int k = klist_p[bp + c];
+    const float2 v = make_float2(pred_mu[2 * (size_t)k], pred_mu[2 * (size_t)k + 1]);
+    bad |= !(finite_f32(v.x) && finite_f32(v.y));
+    s.cen_p[c] = v;
+    s.cused[c] = 0;
+  }
+  if (tid == 0) *n_inv = G;
+  if (__syncthreads_or(bad)) {  // the reference raises (np.min of NaN): no picks, flag set
+    if (tid == 0) {
+      pk.count[f] = 0;
+      atomicExch(bad_value, 1);
+    }
+    return;
+  }
+  for (int round = 0; round < m; ++round) {
+    // 1. rescan: a wave per row over the unused columns.  sq orders as d does except where
+    // two sq round to one d, so the square root is taken only where sq improves
+    const int ninv = *n_inv;
+    for (int i = wave; i < ninv; i += L2_WAVES) {
+      const int r = s.inv[i];
+      const float2 g = s.cen_g[r];
+      float bs = 0.f, bd = 0.f;
+      int bc = -1;
+      for (int c = lane; c < P; c += WAVE) {
+        if (s.cused[c]) continue;
+        const float2 q = s.cen_p[c];
+        const float dx = g.x - q.x, dy = g.y - q.y;
+        const float sq = dx * dx + dy * dy;
+        if (bc < 0 || sq < bs) {
+          const float d = sqrt_rn(sq);
+          if (bc < 0 || d < bd) {
+            bd = d;
+            bc = c;
+          }
+          bs = sq;
+        }
+      }
+      // round < min(G, P): a column is unused, so some lane has one
+      u64 key = bc >= 0 ? ((u64)__float_as_uint(bd) << 32) | (u64)(unsigned)bc : ~(u64)0;
+      key = wave_min_u64(key);
+      if (lane == 0) {
+        s.best_d[r] = __uint_as_float((unsigned)(key >> 32));
+        s.best_c[r] = (int)(unsigned)(key & 0xffffffffu);
+      }
+    }
+    __syncthreads();
+    // 2. the minimum (d, row) of the unused rows; d >= 0 orders as its bits
+    u64 key = ~(u64)0;
+    for (int r = tid; r < G; r += L2_THREADS)
+      if (!s.rused[r]) {
+        const u64 k = ((u64)__float_as_uint(s.best_d[r]) << 32) | (u64)(unsigned)r;
+        key = k < key ? k : key;
+      }
+    key = wave_min_u64(key);
+    if (lane == 0) wkey[wave] = key;
+    if (tid == 0) *n_inv = 0;
+    __syncthreads();
+    key = wkey[0];
+#pragma unroll
+    for (int w = 1; w < L2_WAVES; ++w) key = wkey[w] < key ? wkey[w] : key;
+    const int r1 = (int)(unsigned)(key & 0xffffffffu);
+    const int c1 = s.best_c[r1];
+    // 3. the pick, and the rows that wanted its column
+    if (tid == 0) {
+      const float d = __uint_as_float((unsigned)(key >> 32));
+      const int slot = bg + round;
+      pk.gt[slot] = r1;
+      pk.pred[slot] = c1;
+      pk.d[slot] = d;
+      pk.pos[slot] = d <= eps ? 1 : 0;
+      pk.gt_cluster[slot] = klist_g[bg + r1];
+      pk.pred_cluster[slot] = klist_p[bp + c1];
+      s.rused[r1] = 1;
+      s.cused[c1] = 1;
+    }
+    for (int r = tid; r < G; r += L2_THREADS)
+      if (r != r1 && !s.rused[r] && s.best_c[r] == c1) s.inv[atomicAdd(n_inv, 1)] = r;
+    __syncthreads();
+  }
+  if (tid == 0) pk.count[f] = m;
+}
+
+__global__ __launch_bounds__(L2_THREADS) void l2_assoc_kernel(
+    const int* __restrict__ fbase_g, const int* __restrict__ fend_g,
+    const int* __restrict__ fbase_p, const int* __restrict__ fend_p,
+    const int* __restrict__ klist_g, const int* __restrict__ klist_p,
+    const float* __restrict__ gt_mu, const float* __restrict__ pred_mu, int lds_cap, L2State gws,
+    float eps, Picks pk, int* bad_value) {
+  extern __shared__ __attribute__((aligned(16))) char l2_lds[];
+  __shared__ u64 wkey[L2_WAVES];
+  __shared__ int n_inv;
+  const int f = blockIdx.x;
+  const int bg = fbase_g[f], bp = fbase_p[f];
+  const int G = fend_g[f] - bg, P = fend_p[f] - bp;
+  if (threadIdx.x == 0) pk.start[f] = bg;
+  if (G <= 0 || P <= 0) {
+    if (threadIdx.x == 0) pk.count[f] = 0;
+    return;
+  }
+  if (G <= lds_cap && P <= lds_cap) {
+    L2State s;
+    s.cen_g = (float2*)l2_lds;
+    s.cen_p = s.cen_g + lds_cap;
+    s.best_d = (float*)(s.cen_p + lds_cap);
+    s.best_c = (int*)(s.best_d + lds_cap);
+    s.inv = s.best_c + lds_cap;
+    s.rused = (unsigned char*)(s.inv + lds_cap);
+    s.cused = s.rused + lds_cap;
+    l2_frame(s, f, G, P, bg, bp, klist_g, klist_p, gt_mu, pred_mu, eps, pk, bad_value, wkey,
+             &n_inv);
+  } else {
+    L2State s;
+    s.cen_g = gws.cen_g + bg;
+    s.cen_p = gws.cen_p + bp;
+    s.best_d = gws.best_d + bg;
+    s.best_c = gws.best_c + bg;
+    s.inv = gws.inv + bg;
+    s.rused = gws.rused + bg;
+    s.cused = gws.cused + bp;
+    l2_frame(s, f, G, P, bg, bp, klist_g, klist_p, gt_mu, pred_mu, eps, pk, bad_value, wkey,
+             &n_inv);
+  }
+}
+
 // ------------------------------------------------------------------ accumulation
 
 // LDS bins of one block -> one global atomic per non-zero bin
@@ -506,6 +691,35 @@ static size_t assoc_ws_layout(int n, int nf, AssocWs* w, char* base) {
   return t.off;
 }
 
+struct L2Ws {
+  int *cframe_g, *cframe_p, *krank_g, *krank_p, *klist_g, *klist_p;
+  int* fr;     // [4 F]: fbase_g, fend_g, fbase_p, fend_p (zeroed)
+  L2State st;  // [N] each: the state of the frames past L2_LDS_CAP
+  void* scan_ws;
+};
+
+static size_t l2_ws_layout(int n, int nf, L2Ws* w, char* base) {
+  Taker t{base};
+  L2Ws x;
+  x.cframe_g = t.take<int>(n);
+  x.cframe_p = t.take<int>(n);
+  x.krank_g = t.take<int>((size_t)n + 1);
+  x.krank_p = t.take<int>((size_t)n + 1);
+  x.klist_g = t.take<int>(n);
+  x.klist_p = t.take<int>(n);
+  x.fr = t.take<int>((size_t)4 * nf);
+  x.st.cen_g = t.take<float2>(n);
+  x.st.cen_p = t.take<float2>(n);
+  x.st.best_d = t.take<float>(n);
+  x.st.best_c = t.take<int>(n);
+  x.st.inv = t.take<int>(n);
+  x.st.rused = t.take<unsigned char>(n);
+  x.st.cused = t.take<unsigned char>(n);
+  x.scan_ws = t.take<char>(scan_workspace_bytes((long)n + 1));
+  if (w) *w = x;
+  return t.off;
+}
+
 }  // namespace eval
 }  // namespace rg
 
@@ -675,6 +889,82 @@ extern "C" int rg_eval_associate(const int* frame_ptr, int n_nodes, int n_frames
   walk_kernel<<<nf, WAVE, 0, st>>>(est, eend, ws.vals2_s, ws.ent_g, ws.ent_p, ws.ent_d, ws.krank_g,
                                    ws.krank_p, fbase_g, fend_g, fbase_p, fend_p, ws.klist_g,
                                    ws.klist_p, used_g, used_p, ws.unr, ws.unc, eps, pk);
+  RG_LAUNCH_CHECK();
+  return RG_OK;
+}
+
+extern "C" size_t rg_eval_associate_l2_workspace_size(int n_nodes, int n_frames) {
+  if (n_nodes <= 0 || n_frames <= 0 || n_nodes > EVAL_MAX_NODES) return 0;
+  return l2_ws_layout(n_nodes, n_frames, nullptr, nullptr);
+}
+
+extern "C" int rg_eval_associate_l2(const int* frame_ptr, int n_nodes, int n_frames,
+                                    int max_frame_nodes, const int* gt_ptr, const int* gt_idx,
+                                    const int* pred_ptr, const int* pred_idx, int size_threshold,
+                                    float eps, const float* gt_mu, const float* pred_mu,
+                                    int* gt_kept, int* pred_kept, int* pick_start,
+                                    int* pick_count, int* pick_gt, int* pick_pred, float* pick_d,
+                                    int* pick_positive, int* pick_gt_cluster,
+                                    int* pick_pred_cluster, int* bad_value, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  RG_REQUIRE(n_nodes >= 0 && n_frames >= 0 && max_frame_nodes >= 0 && size_threshold >= 0,
+             RG_ERR_ARG,
+             "rg_eval_associate_l2: n_nodes=%d n_frames=%d max_frame_nodes=%d threshold=%d",
+             n_nodes, n_frames, max_frame_nodes, size_threshold);
+  RG_REQUIRE(n_nodes <= EVAL_MAX_NODES, RG_ERR_UNSUPPORTED, "rg_eval_associate_l2: n_nodes=%d > %d",
+             n_nodes, EVAL_MAX_NODES);
+  RG_REQUIRE(n_nodes == 0 || n_frames >= 1, RG_ERR_ARG,
+             "rg_eval_associate_l2: nodes without a frame");
+  if (n_frames == 0) return RG_OK;
+  RG_REQUIRE(pick_start && pick_count, RG_ERR_ARG, "rg_eval_associate_l2: null pick_start / pick_count");
+  if (n_nodes == 0) {
+    RG_CHECK_HIP(hipMemsetAsync(pick_start, 0, (size_t)n_frames * sizeof(int), st));
+    RG_CHECK_HIP(hipMemsetAsync(pick_count, 0, (size_t)n_frames * sizeof(int), st));
+    return RG_OK;
+  }
+  RG_REQUIRE(frame_ptr && gt_ptr && gt_idx && pred_ptr && pred_idx && gt_mu && pred_mu && gt_kept &&
+                 pred_kept && pick_gt && pick_pred && pick_d && pick_positive && pick_gt_cluster &&
+                 pick_pred_cluster && bad_value,
+             RG_ERR_ARG, "rg_eval_associate_l2: null pointer with n_nodes=%d", n_nodes);
+  L2Ws ws;
+  const size_t need = l2_ws_layout(n_nodes, n_frames, &ws, (char*)workspace);
+  RG_REQUIRE(workspace && workspace_bytes >= need, RG_ERR_ARG,
+             "rg_eval_associate_l2: workspace %zu < %zu", workspace_bytes, need);
+  const int n = n_nodes, nf = n_frames, nb = ceil_div(n, 256);
+  int *fbase_g = ws.fr, *fend_g = ws.fr + nf, *fbase_p = ws.fr + 2 * (size_t)nf,
+      *fend_p = ws.fr + 3 * (size_t)nf;
+  RG_CHECK_HIP(hipMemsetAsync(ws.fr, 0, (size_t)4 * nf * sizeof(int), st));
+  RG_CHECK_HIP(hipMemsetAsync(pick_gt_cluster, 0xff, (size_t)n * sizeof(int), st));
+  RG_CHECK_HIP(hipMemsetAsync(pick_pred_cluster, 0xff, (size_t)n * sizeof(int), st));
+
+  // the size filter and each frame's kept clusters, as rg_eval_associate
+  cluster_info_kernel<<<nb, 256, 0, st>>>(gt_ptr, gt_idx, frame_ptr, nf, n, size_threshold,
+                                          gt_kept, ws.cframe_g);
+  cluster_info_kernel<<<nb, 256, 0, st>>>(pred_ptr, pred_idx, frame_ptr, nf, n, size_threshold,
+                                          pred_kept, ws.cframe_p);
+  RG_LAUNCH_CHECK();
+  int rc = exclusive_scan(gt_kept, n, ws.krank_g, nullptr, ws.scan_ws, st);
+  if (rc) return rc;
+  rc = exclusive_scan(pred_kept, n, ws.krank_p, nullptr, ws.scan_ws, st);
+  if (rc) return rc;
+  cluster_frames_kernel<<<nb, 256, 0, st>>>(gt_kept, ws.cframe_g, ws.krank_g, n, fbase_g, fend_g,
+                                            ws.klist_g);
+  cluster_frames_kernel<<<nb, 256, 0, st>>>(pred_kept, ws.cframe_p, ws.krank_p, n, fbase_p,
+                                            fend_p, ws.klist_p);
+  RG_LAUNCH_CHECK();
+
+  // a frame has at most max_frame_nodes clusters a side; one past the LDS state (or past a
+  // max_frame_nodes that was too small) runs from the workspace
+  int cap = max_frame_nodes < L2_LDS_CAP ? max_frame_nodes : L2_LDS_CAP;
+  if (cap < 1) cap = 1;
+  const int lds_bytes = (cap * L2_SLOT_BYTES + 15) & ~15;
+  RG_ENSURE_LDS(l2_assoc_kernel, ((L2_LDS_CAP * L2_SLOT_BYTES + 15) & ~15));
+  Picks pk{pick_start, pick_count, pick_gt, pick_pred, pick_d, pick_positive, pick_gt_cluster,
+           pick_pred_cluster};
+  l2_assoc_kernel<<<nf, L2_THREADS, lds_bytes, st>>>(fbase_g, fend_g, fbase_p, fend_p, ws.klist_g,
+                                                     ws.klist_p, gt_mu, pred_mu, cap, ws.st, eps,
+                                                     pk, bad_value);
   RG_LAUNCH_CHECK();
   return RG_OK;
 }

@@ -8,6 +8,9 @@ for batches of frames:
   associate                          the size filter of detection_accuracy.py:141-164 and
                                      compute_gt_and_pred_associations (:192-273), all frames
   compute_gt_and_pred_associations   the drop-in for the reference function (one frame)
+  cluster_centres, associate_l2      the same association under the 'l2_norm' criterion: the
+                                     float32 distance between cluster centres (:211-213, 225)
+  compute_gt_and_pred_associations_l2  the drop-in with that criterion (one frame)
   DetectionEvaluator                 performance_eval_detection.ipynb: confusion matrix,
                                      ground-truth and prediction counts, precision, recall
   SegmentationEvaluator              performance_eval_segmentation.ipynb: node-level confusion
@@ -169,9 +172,85 @@ def associate(frame_ptr, gt_of, gt_ptr, gt_idx, pred_of, pred_ptr, pred_idx, eps
     return out
 
 
+def cluster_centres(xy, cluster_ptr, cluster_idx):
+    """float32 [N, 2]: the centre (sample mean of the members' positions) of every cluster of a
+    CSR over N nodes, indexed by cluster id, 0 in the slots past the last cluster
+    (rg_cluster_stats over the padded CSR: compute_proposals' means bit for bit).  xy float32
+    [N, >= 2] on the device."""
+    torch = _torch()
+    xy = xy.detach()
+    if xy.dim() != 2 or int(xy.shape[1]) < 2:
+        raise ValueError(f'expected [N, >= 2] positions, got {tuple(xy.shape)}')
+    if xy.dtype != torch.float32:
+        xy = xy.to(torch.float32)
+    if xy.shape[0] > 0 and xy.stride(1) != 1:
+        xy = xy.contiguous()
+    dev = xy.device
+    N = int(xy.shape[0])
+    mu = torch.zeros((max(N, 1), 2), dtype=torch.float32, device=dev)
+    if N > 0:
+        ptr = _full_ptr(cluster_ptr, N)
+        idx = cluster_idx.to(torch.int32).contiguous()
+        size = _i32(dev, N)
+        sigma = torch.empty((N, 4), dtype=torch.float32, device=dev)
+        bad = _i32(dev, 1, 0)
+        noise = np.zeros(4, dtype=np.float32)
+        nat.check(nat.lib().rg_cluster_stats(
+            xy.data_ptr(), xy.stride(0), N, ptr.data_ptr(), idx.data_ptr(), N, noise.ctypes.data,
+            size.data_ptr(), mu.data_ptr(), sigma.data_ptr(), None, None, bad.data_ptr(),
+            nat.stream_ptr(dev)), 'rg_cluster_stats')
+    return mu[:N]
+
+
+def associate_l2(frame_ptr, gt_ptr, gt_idx, pred_ptr, pred_idx, gt_mu, pred_mu, eps: float,
+                 cluster_size_threshold: int = 0, max_frame_nodes: Optional[int] = None,
+                 ws_cache: Optional[dict] = None) -> dict:
+    """Size filter + greedy association of every frame by the float32 distance between cluster
+    centres, the reference's 'l2_norm' criterion (rg_eval_associate_l2).  The CSRs are int32
+    device tensors over the batch's N nodes (``*_ptr`` with N + 1 entries); gt_mu / pred_mu
+    float32 [N, 2] hold the centres by cluster id (``cluster_centres``).  Returns the dict
+    ``associate`` returns (``frame_picks`` reads it) plus bad_value int32 [1], set when a kept
+    cluster of a frame with picks to make has a centre that is not finite (such a frame has no
+    picks; the reference raises).  Distances of 9,999,999 or more are outside the domain."""
+    torch = _torch()
+    dev = gt_ptr.device
+    N, F = int(gt_ptr.shape[0]) - 1, int(frame_ptr.shape[0]) - 1
+    lib = nat.lib()
+    mus = []
+    for name, mu in (('gt_mu', gt_mu), ('pred_mu', pred_mu)):
+        if mu.dtype != torch.float32 or tuple(mu.shape) != (N, 2):
+            raise ValueError(f'{name}: expected float32 [{N}, 2], got {mu.dtype} '
+                             f'{tuple(mu.shape)}')
+        mus.append(mu.contiguous())
+    out = dict(gt_kept=_i32(dev, N), pred_kept=_i32(dev, N), pick_start=_i32(dev, F),
+               pick_count=_i32(dev, F), pick_gt=_i32(dev, N), pick_pred=_i32(dev, N),
+               pick_d=torch.empty(max(N, 1), dtype=torch.float32, device=dev),
+               pick_positive=_i32(dev, N), pick_gt_cluster=_i32(dev, N),
+               pick_pred_cluster=_i32(dev, N), bad_value=_i32(dev, 1, 0))
+    wsz = lib.rg_eval_associate_l2_workspace_size(N, F)
+    ws = _workspace(ws_cache, 'eval_assoc_l2_ws', wsz, dev)
+    maxn = N if max_frame_nodes is None else int(max_frame_nodes)
+    nat.check(lib.rg_eval_associate_l2(
+        frame_ptr.data_ptr(), N, F, maxn, gt_ptr.data_ptr(), gt_idx.data_ptr(),
+        pred_ptr.data_ptr(), pred_idx.data_ptr(), int(cluster_size_threshold), float(eps),
+        mus[0].data_ptr(), mus[1].data_ptr(), out['gt_kept'].data_ptr(),
+        out['pred_kept'].data_ptr(), out['pick_start'].data_ptr(), out['pick_count'].data_ptr(),
+        out['pick_gt'].data_ptr(), out['pick_pred'].data_ptr(), out['pick_d'].data_ptr(),
+        out['pick_positive'].data_ptr(), out['pick_gt_cluster'].data_ptr(),
+        out['pick_pred_cluster'].data_ptr(), out['bad_value'].data_ptr(), ws.data_ptr(), wsz,
+        nat.stream_ptr(dev)), 'rg_eval_associate_l2')
+    for k in ('pick_start', 'pick_count'):
+        out[k] = out[k][:F]
+    for k in ('gt_kept', 'pred_kept', 'pick_gt', 'pick_pred', 'pick_d', 'pick_positive',
+              'pick_gt_cluster', 'pick_pred_cluster'):
+        out[k] = out[k][:N]
+    return out
+
+
 def frame_picks(assoc: dict) -> List[dict]:
-    """The picks of ``associate`` per frame, on the host (one synchronisation): a list of
-    dicts with gt, pred (int32), d (float32) and positive (bool) arrays in pick order."""
+    """The picks of ``associate`` / ``associate_l2`` per frame, on the host (one
+    synchronisation): a list of dicts with gt, pred (int32), d (float32) and positive (bool)
+    arrays in pick order."""
     h = {k: v.cpu().numpy() for k, v in assoc.items() if k.startswith('pick_')}
     out = []
     for s, c in zip(h['pick_start'], h['pick_count']):
@@ -205,11 +284,12 @@ def compute_gt_and_pred_associations(det_and_gt_clusters, eps, association_crite
                                      false_class_label=6, device=None):
     """Drop-in for detection_accuracy.compute_gt_and_pred_associations (:192-273): the same
     dict of lists in, the same four numpy arrays out, element for element; the association
-    runs on the GPU.  'l2_norm' (a dense matrix the notebooks do not use) is not built."""
+    runs on the GPU.  This entry point is the 'inv_iou' criterion; 'l2_norm' is
+    ``compute_gt_and_pred_associations_l2`` and keeps raising here."""
     torch = _torch()
     if association_criteria == 'l2_norm':
-        raise NotImplementedError("association_criteria='l2_norm' is not implemented "
-                                  "(the evaluation notebooks use 'inv_iou')")
+        raise NotImplementedError("association_criteria='l2_norm' is not implemented by this "
+                                  "function: call compute_gt_and_pred_associations_l2")
     if association_criteria != 'inv_iou':
         raise ValueError(f'association_criteria {association_criteria!r}')
     d = det_and_gt_clusters
@@ -234,7 +314,13 @@ def compute_gt_and_pred_associations(det_and_gt_clusters, eps, association_crite
     fptr = up(np.array([0, N], dtype=np.int32))
     res = associate(fptr, up(g_of), up(g_ptr), up(g_idx), up(p_of), up(p_ptr), up(p_idx),
                     float(eps), cluster_size_threshold=0)
-    pk = frame_picks(res)[0]
+    return _associated_arrays(frame_picks(res)[0], obj_class_gt, obj_class_pred,
+                              false_class_label)
+
+
+def _associated_arrays(pk, obj_class_gt, obj_class_pred, false_class_label):
+    """detection_accuracy.py:237-273 from one frame's picks: the positive picks' classes, then
+    the negative picks' predicted classes against ``false_class_label``."""
     pos = pk['positive']
     gi, pi = pk['gt'].astype(np.int64), pk['pred'].astype(np.int64)
     pos_gt = obj_class_gt[gi[pos]]
@@ -244,6 +330,54 @@ def compute_gt_and_pred_associations(det_and_gt_clusters, eps, association_crite
     return {'obj_class_gt_associated': np.concatenate((pos_gt, neg_gt), axis=0),
             'obj_class_pred_associated': np.concatenate((pos_pred, neg_pred), axis=0),
             'obj_class_gt': obj_class_gt, 'obj_class_pred': obj_class_pred}
+
+
+def _centre_rows(means, n_rows: int, what: str) -> np.ndarray:
+    out = np.zeros((n_rows, 2), dtype=np.float32)
+    for i, m in enumerate(means):
+        m = np.asarray(m)
+        if m.dtype != np.float32:
+            raise TypeError(f'cluster_mean_list_{what}[{i}] is {m.dtype}, expected the float32 '
+                            'means compute_proposals returns')
+        if m.shape != (2,):
+            raise ValueError(f'cluster_mean_list_{what}[{i}] has shape {m.shape}, expected (2,)')
+        out[i] = m
+    return out
+
+
+def compute_gt_and_pred_associations_l2(det_and_gt_clusters, eps, false_class_label=6,
+                                        device=None):
+    """detection_accuracy.compute_gt_and_pred_associations (:192-273) with
+    association_criteria='l2_norm': the same dict in, the same four numpy arrays out (the
+    float64 empties of conditions 2-4 included); the association runs on the GPU
+    (``associate_l2``).  Only ``cluster_mean_list_*`` (float32 [2] arrays, as compute_proposals
+    returns them; any other dtype is a TypeError) and ``obj_class_*`` are read, not the member
+    sets.  A centre that is not finite is a ValueError (the reference fails on np.min of NaN)."""
+    torch = _torch()
+    d = det_and_gt_clusters
+    n_pred, n_gt = len(d['cluster_mean_list_pred']), len(d['cluster_mean_list_gt'])
+    empty = np.zeros(shape=(0, ))
+    if n_pred == 0 or n_gt == 0:
+        return {'obj_class_gt_associated': empty, 'obj_class_pred_associated': empty,
+                'obj_class_gt': np.array(d['obj_class_gt']) if n_gt > 0 else empty,
+                'obj_class_pred': np.array(d['obj_class_pred']) if n_pred > 0 else empty}
+    obj_class_pred = np.array(d['obj_class_pred'])
+    obj_class_gt = np.array(d['obj_class_gt'])
+    # one frame of N = max(G, P) nodes; cluster i of either side is the node i
+    N = max(n_gt, n_pred)
+    g_mu = _centre_rows(d['cluster_mean_list_gt'], N, 'gt')
+    p_mu = _centre_rows(d['cluster_mean_list_pred'], N, 'pred')
+    dev = torch.device(device) if device is not None else torch.device('cuda',
+                                                                       torch.cuda.current_device())
+    up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    ptr = lambda n: up(np.minimum(np.arange(N + 1), n).astype(np.int32))  # noqa: E731
+    idx = up(np.arange(N, dtype=np.int32))
+    res = associate_l2(up(np.array([0, N], dtype=np.int32)), ptr(n_gt), idx, ptr(n_pred), idx,
+                       up(g_mu), up(p_mu), float(eps), cluster_size_threshold=0)
+    pk = frame_picks(res)[0]
+    if int(res['bad_value'].item()):
+        raise ValueError('a cluster centre is not finite')
+    return _associated_arrays(pk, obj_class_gt, obj_class_pred, false_class_label)
 
 
 # ------------------------------------------------------------------------- reporting
@@ -310,7 +444,8 @@ class _Counters:
         if self._dev is None:
             self._dev = {k: torch.zeros(self._shape(k), dtype=torch.int64, device=dev)
                          for k in self.NAMES}
-            self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
+            # [0]: a class id out of range, [1]: a centre that is not finite ('l2_norm')
+            self._bad = torch.zeros(2, dtype=torch.int32, device=dev)
         elif self._bad.device != dev:
             raise ValueError(f'evaluator lives on {self._bad.device}, update came from {dev}')
         return self._dev
@@ -321,8 +456,11 @@ class _Counters:
             torch = _torch()
             flat = torch.cat([self._dev[k].reshape(-1) for k in self.NAMES]
                              + [self._bad.to(torch.int64)]).cpu().numpy()
-            if flat[-1]:
+            if flat[-2]:
                 raise RuntimeError('a class id outside [0, num_classes) reached the evaluator')
+            if flat[-1]:
+                raise RuntimeError("a cluster centre that is not finite reached the 'l2_norm' "
+                                   'association (the reference raises on such a frame)')
             off = 0
             for k in self.NAMES:
                 n = int(np.prod(self._shape(k)))
@@ -359,14 +497,21 @@ class _Counters:
 
 class DetectionEvaluator(_Counters):
     """performance_eval_detection.ipynb on the device: per batch the ground-truth clusters from
-    the track keys, the predicted clusters' classes, the size filter, the greedy 1 - IoU
-    association (compute_gt_and_pred_associations) and the three count matrices."""
+    the track keys, the predicted clusters' classes, the size filter, the greedy association
+    (compute_gt_and_pred_associations) and the three count matrices.  association_criteria is
+    the reference's: 'inv_iou' (1 - IoU of the member sets) or 'l2_norm' (the float32 distance
+    between the cluster centres, which needs the node positions: ``update(..., xy=)``)."""
 
     NAMES = ('confusion_matrix', 'gt_count_matrix', 'pred_count_matrix')
 
     def __init__(self, num_classes: int = 7, eps: float = 0.7, cluster_size_threshold: int = 0,
-                 by_segmentation: bool = True, false_class_label: int = 6):
+                 by_segmentation: bool = True, false_class_label: int = 6,
+                 association_criteria: str = 'inv_iou'):
         super().__init__(num_classes)
+        if association_criteria not in ('inv_iou', 'l2_norm'):
+            raise ValueError(f"association_criteria {association_criteria!r}: "
+                             "'inv_iou' or 'l2_norm'")
+        self.association_criteria = association_criteria
         if not 0 <= int(false_class_label) < self.num_classes:
             raise ValueError(f'false_class_label={false_class_label} outside [0, {num_classes})')
         if int(cluster_size_threshold) < 0:
@@ -377,18 +522,24 @@ class DetectionEvaluator(_Counters):
         self.false_class_label = int(false_class_label)
 
     def update(self, node_cls, obj_cls, pred_cluster_ptr, pred_cluster_idx, node_gt_class,
-               track_key, frame_ptr, max_frame_nodes: Optional[int] = None):
+               track_key, frame_ptr, max_frame_nodes: Optional[int] = None, xy=None):
         """One batch, every tensor on the device, no host synchronisation.  node_cls f32
         [N, C] logits, obj_cls f32 [clusters, C] logits (read only when not by_segmentation),
         pred_cluster_ptr / pred_cluster_idx the predicted clusters' CSR over global node ids
         (as engine.propose_clusters returns them), node_gt_class [N], track_key int32 [N]
         (0 = no track), frame_ptr int32 [F + 1].  max_frame_nodes bounds the largest frame
-        (default: N); it must stay below 2^24.  ``self.last`` keeps the batch's device
-        tensors (ground-truth clusters, predicted classes, picks) until the next update."""
+        (default: N); it must stay below 2^24 under 'inv_iou'.  xy float32 [N, >= 2]: the
+        node positions, required under 'l2_norm' and ignored under 'inv_iou'.  ``self.last``
+        keeps the batch's device tensors (ground-truth clusters, predicted classes, picks;
+        under 'l2_norm' also the centres gt_mu / pred_mu by cluster id) until the next
+        update."""
         torch = _torch()
         dev = node_cls.device
         if dev.type != 'cuda':
             raise ValueError('DetectionEvaluator.update needs device tensors')
+        l2 = self.association_criteria == 'l2_norm'
+        if l2 and xy is None:
+            raise ValueError("association_criteria='l2_norm' needs the node positions (xy)")
         lib = nat.lib()
         st = nat.stream_ptr(dev)
         acc = self._device_counters(dev)
@@ -413,8 +564,20 @@ class DetectionEvaluator(_Counters):
                 raise ValueError(f'obj_cls has {obj_cls.shape[0]} rows for {ncl} clusters')
             p_cls = argmax_rows(obj_cls) if ncl > 0 else torch.zeros(1, dtype=torch.int64,
                                                                      device=dev)
-        res = associate(fptr, gt['cluster_of'], gt['cluster_ptr'], gt['cluster_idx'], p_of, p_ptr,
-                        p_idx, self.eps, self.cluster_size_threshold, max_frame_nodes, self._ws)
+        if l2:
+            if int(xy.shape[0]) != N:
+                raise ValueError(f'xy has {xy.shape[0]} rows for {N} nodes')
+            gt_mu = cluster_centres(xy, gt['cluster_ptr'], gt['cluster_idx'])
+            pred_mu = cluster_centres(xy, p_ptr, p_idx)
+            res = associate_l2(fptr, gt['cluster_ptr'], gt['cluster_idx'], p_ptr, p_idx, gt_mu,
+                               pred_mu, self.eps, self.cluster_size_threshold, max_frame_nodes,
+                               self._ws)
+            # the kernel sets, never clears: one flag serves every update
+            self._bad[1:].bitwise_or_(res['bad_value'])
+        else:
+            res = associate(fptr, gt['cluster_of'], gt['cluster_ptr'], gt['cluster_idx'], p_of,
+                            p_ptr, p_idx, self.eps, self.cluster_size_threshold, max_frame_nodes,
+                            self._ws)
         nat.check(lib.rg_eval_accumulate(
             res['pick_gt_cluster'].data_ptr(), res['pick_pred_cluster'].data_ptr(),
             res['pick_positive'].data_ptr(), res['gt_kept'].data_ptr(),
@@ -423,13 +586,15 @@ class DetectionEvaluator(_Counters):
             acc['gt_count_matrix'].data_ptr(), acc['pred_count_matrix'].data_ptr(),
             self._bad.data_ptr(), st), 'rg_eval_accumulate')
         self.last = dict(gt=gt, pred_class=p_cls[:ncl], assoc=res)
+        if l2:
+            self.last.update(gt_mu=gt_mu, pred_mu=pred_mu)
         return self
 
-    def update_frames(self, detector_outputs, node_gt_class, track_key):
+    def update_frames(self, detector_outputs, node_gt_class, track_key, xy=None):
         """A batch straight from ``Model_Inference.forward_frames(..., cluster_node_idx=None,
         other_features)``: its 5-tuple (node_cls, node_reg, link_cls, obj_cls, per-frame lists
         of frame-local member indices), with the per-frame lists of ground-truth node classes
-        and track keys."""
+        and track keys and, under 'l2_norm', of node positions (xy: float32 [n, >= 2] each)."""
         torch = _torch()
         node_cls, _, _, obj_cls, lists = detector_outputs
         dev = node_cls.device
@@ -451,9 +616,15 @@ class DetectionEvaluator(_Counters):
         fptr = torch.from_numpy(bases.astype(np.int32)).to(dev)
         cat = lambda ts, dt: torch.cat([torch.as_tensor(t).reshape(-1).to(dev, dt)  # noqa: E731
                                         for t in ts]) if ts else torch.zeros(0, dtype=dt, device=dev)
+        pos = None
+        if self.association_criteria == 'l2_norm':
+            if xy is None or len(xy) != len(sizes):
+                raise ValueError("association_criteria='l2_norm' needs one xy array per frame")
+            pos = (torch.cat([torch.as_tensor(t)[:, :2].to(dev, torch.float32) for t in xy])
+                   if sizes else torch.zeros((0, 2), dtype=torch.float32, device=dev))
         return self.update(node_cls, obj_cls, ptr, idx, cat(node_gt_class, torch.int64),
                            cat(track_key, torch.int32), fptr,
-                           max_frame_nodes=max(sizes) if sizes else 0)
+                           max_frame_nodes=max(sizes) if sizes else 0, xy=pos)
 
     def result(self, invalid_class_index: Optional[int] = INVALID_CLS_IDX) -> dict:
         """One synchronisation: the three count matrices (numpy uint64) and the notebook's
@@ -524,8 +695,9 @@ def evaluate_window_batch(win, model, cfg, detection: Optional[DetectionEvaluato
     out = det.outputs
     gt_class = fb.labels['class_labels']
     if detection is not None:
+        xy = det.xy if detection.association_criteria == 'l2_norm' else None
         detection.update(out.node_cls, out.obj_cls, out.cluster_ptr, out.cluster_idx, gt_class,
-                         fb.track_key, fb.frame_ptr, max_frame_nodes=max(fb.frame_sizes))
+                         fb.track_key, fb.frame_ptr, max_frame_nodes=max(fb.frame_sizes), xy=xy)
     if segmentation is not None:
         segmentation.update(out.node_cls, gt_class)
     return fb, out

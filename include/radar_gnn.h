@@ -1082,6 +1082,35 @@ int rg_eval_associate(const int* frame_ptr, int n_nodes, int n_frames, int max_f
                       int* pick_gt_cluster, int* pick_pred_cluster, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* The same association under the 'l2_norm' criterion (detection_accuracy.py:211-213, 225): the
+ * G x P matrix of a frame's kept clusters holds the Euclidean distance between their centres,
+ * gt_mu / pred_mu float32 [N][2] indexed by cluster id (the mu of rg_cluster_stats over the
+ * padded CSRs; an empty slot is never read).  min(G, P) rounds: a round picks the minimum of
+ * the remaining matrix, on equal distances the lowest row and then the lowest column
+ * (np.nonzero(dist == np.min(dist))[0]), and the picked row and column leave the matrix.
+ * Arithmetic: d = sqrt(fl(fl(dx dx) + fl(dy dy))) in float32, two rounded products, one add, a
+ * correctly rounded square root, never contracted: numpy's np.linalg.norm(.., axis=-1) bit for
+ * bit.  pick_d = d, pick_positive = d <= eps; every output has the layout of
+ * rg_eval_associate, so rg_eval_accumulate consumes it unchanged.
+ * Domain: a frame with picks to make in which a kept cluster's centre is not finite gets no
+ * picks and sets *bad_value (device int32, caller-zeroed; the reference raises there).
+ * Distances of 9,999,999 or more meet the reference's VERY_LARGE_NUM sentinel and are outside
+ * the domain (picks stay well defined here).
+ * Cost: the matrix is never stored (workspace O(N + F)).  One workgroup per frame recomputes
+ * distances from the centres: G P up front, P per row whose cached nearest column was taken
+ * by another row -- O(min(G, P) G P) in the worst case, where every row keeps wanting the same
+ * column.  max_frame_nodes (an upper bound of a frame's clusters a side) sizes the LDS of the
+ * launch; a frame with more than 4096 kept clusters a side, or more than max_frame_nodes,
+ * keeps its state in the workspace instead. */
+size_t rg_eval_associate_l2_workspace_size(int n_nodes, int n_frames);
+int rg_eval_associate_l2(const int* frame_ptr, int n_nodes, int n_frames, int max_frame_nodes,
+                         const int* gt_ptr, const int* gt_idx, const int* pred_ptr,
+                         const int* pred_idx, int size_threshold, float eps, const float* gt_mu,
+                         const float* pred_mu, int* gt_kept, int* pred_kept, int* pick_start,
+                         int* pick_count, int* pick_gt, int* pick_pred, float* pick_d,
+                         int* pick_positive, int* pick_gt_cluster, int* pick_pred_cluster,
+                         int* bad_value, void* workspace, size_t workspace_bytes, void* stream);
+
 /* performance_eval_detection.ipynb: confusion[gt][pred] += 1 per pick (a negative pick's gt
  * class is false_class), gt_count[class] += 1 per kept ground-truth cluster, pred_count[class]
  * += 1 per kept predicted cluster; int64 device accumulators ([nc][nc], [nc], [nc]) kept by
