@@ -162,10 +162,13 @@ _SIGNATURES = {
                                   _P, _P, _P, _P, _P, _P, _P, _P, _S, _P]),
     'rg_eval_accumulate': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     'rg_eval_node_confusion': (_I, [_P, _I, _P, _L, _I, _P, _P, _P, _P]),
+    'rg_eval_class_confusion': (_I, [_P, _P, _L, _I, _P, _P, _P, _P]),
     # object stage (objects.hip)
     'rg_cluster_stats': (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     'rg_cov_ellipse': (_I, [_P, _P, _P, _I, _F, _I, _P, _P, _P]),
     'rg_softmax_max': (_I, [_P, _I, _L, _I, _P, _P, _P]),
+    'rg_cluster_class_from_objects': (_I, [_P, _I, _L, _I, _P, _I, ctypes.c_int64, _P, _P, _P,
+                                           _P]),
     'rg_object_select_workspace_size': (_S, [_I]),
     'rg_object_select': (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _S,
                               _P]),

@@ -703,3 +703,27 @@ def validate_classifier_sequence(store, detector, model_training, cfg, indices,
     if vals.size == 0:
         return float('nan'), 0
     return float(np.mean(vals, dtype=np.float64)), int(vals.size)
+
+
+def evaluate_classifier_sequence(store, detector, classifier_model, cfg, indices,
+                                 window_size: int = 10, batch_windows: int = 64,
+                                 min_meas: int = 2, meas_noise_cov=None, evaluator=None):
+    """The accuracy validate_classifier_sequence lacks: the same walk (no flip, no_grad, a
+    ``SequenceStore`` or a ``SequenceSet``) with every kept proposal's predicted class -- the
+    first maximum of its logits -- counted against its majority ground-truth class, lowest
+    label on a tie (datagen_classifier.py:50-60), in an ``evaluation.ObjectClassEvaluator``
+    (new unless given).  Nothing is read back: ``result()`` of the returned evaluator is the
+    only read of the counters.  Weights, optimizer state and applied steps are untouched."""
+    from .. import evaluation, objects
+    if evaluator is None:
+        evaluator = evaluation.ObjectClassEvaluator(int(cfg.num_classes))
+    cache: dict = {}
+    with torch.no_grad():
+        for _, pos in _batches(indices, batch_windows):
+            inp = _sequence_inputs(store, detector, cfg, pos, window_size, None, min_meas,
+                                   meas_noise_cov, cache)
+            if inp is None or inp.n_objects == 0:
+                continue
+            evaluator.update_logits(objects.classify_inputs(classifier_model, inp),
+                                    inp.object_class)
+    return evaluator

@@ -18,7 +18,9 @@
 //                           of centre distances, recomputed from the centres by one workgroup
 //                           per frame and never stored (see l2_assoc_kernel);
 //   rg_eval_accumulate    : the notebook's confusion / gt_count / pred_count updates;
-//   rg_eval_node_confusion: the segmentation notebook's node-level confusion matrix.
+//   rg_eval_node_confusion: the segmentation notebook's node-level confusion matrix;
+//   rg_eval_class_confusion: the same matrix over rows whose prediction is a class id already
+//                           (the object-level confusion of the two-stage flow).
 // The accumulators are int64: integer adds make them independent of the arrival order.  Each
 // block sums in LDS first and then issues one global atomic per non-zero bin.
 #include "rg_common.h"
@@ -594,6 +596,30 @@ __global__ __launch_bounds__(256) void node_confusion_kernel(
   flush_bins(bins, nbins, dst, first, 2);
 }
 
+// the same counts for predictions that are class ids already
+__global__ __launch_bounds__(256) void class_confusion_kernel(
+    const int64_t* __restrict__ gt, const int64_t* __restrict__ pred, long n, int nc,
+    int64_t* confusion, int64_t* gt_count, int* __restrict__ bad) {
+  __shared__ int bins[MAXC * MAXC + MAXC];
+  const int nbins = nc * nc + nc;
+  for (int b = threadIdx.x; b < nbins; b += blockDim.x) bins[b] = 0;
+  __syncthreads();
+  for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < n;
+       r += (long)gridDim.x * blockDim.x) {
+    const int64_t c = gt[r], p = pred[r];
+    if (c < 0 || c >= nc || p < 0 || p >= nc) {
+      atomicExch(bad, 1);
+      continue;
+    }
+    atomicAdd(bins + (int)c * nc + (int)p, 1);
+    atomicAdd(bins + nc * nc + (int)c, 1);
+  }
+  __syncthreads();
+  int64_t* dst[2] = {confusion, gt_count};
+  const int first[2] = {0, nc * nc};
+  flush_bins(bins, nbins, dst, first, 2);
+}
+
 // ------------------------------------------------------------------ workspaces
 
 static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -1003,6 +1029,23 @@ extern "C" int rg_eval_node_confusion(const float* node_logits, int ld, const in
   node_confusion_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(node_logits, ld, node_class, n_nodes,
                                                              num_classes, confusion, gt_count,
                                                              bad_class);
+  RG_LAUNCH_CHECK();
+  return RG_OK;
+}
+
+extern "C" int rg_eval_class_confusion(const int64_t* gt_class, const int64_t* pred_class, long n,
+                                       int num_classes, int64_t* confusion, int64_t* gt_count,
+                                       int* bad_class, void* stream) {
+  RG_REQUIRE(n >= 0, RG_ERR_ARG, "rg_eval_class_confusion: n=%ld", n);
+  RG_REQUIRE(num_classes >= 1 && num_classes <= MAXC, RG_ERR_UNSUPPORTED,
+             "rg_eval_class_confusion: num_classes=%d outside 1..%d", num_classes, MAXC);
+  if (n == 0) return RG_OK;
+  RG_REQUIRE(gt_class && pred_class && confusion && gt_count && bad_class, RG_ERR_ARG,
+             "rg_eval_class_confusion: null pointer with n=%ld", n);
+  int nb = ceil_div(n, 256);
+  if (nb > 1024) nb = 1024;
+  class_confusion_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(gt_class, pred_class, n, num_classes,
+                                                              confusion, gt_count, bad_class);
   RG_LAUNCH_CHECK();
   return RG_OK;
 }

@@ -6,6 +6,8 @@
 //                        the symmetric 2 x 2 covariance (LAPACK sgeev -> slanv2: order and sign);
 //   rg_cov_ellipse     : compute_cov_ellipse (modules/inference/ellipse.py:4-37);
 //   rg_softmax_max     : torch.max(F.softmax(logits)) of process_frame (output.py:104-121);
+//   rg_cluster_class_from_objects : the same per kept object of the cluster-level classifier,
+//                        scattered to the object's source cluster (the third class source);
 //   rg_object_select   : the size filter (remove_low_quality_proposals,
 //                        datagen_classifier.py:166-190) and the class filter (output.py:123-128)
 //                        with the compaction of the kept objects and of their member rows;
@@ -162,13 +164,12 @@ __global__ void ellipse_points_kernel(const float* __restrict__ abt, const float
   pts[2 * t + 1] = (float)(-px * st + py * ct + (double)mu[2 * c + 1]);
 }
 
-__global__ void softmax_max_kernel(const float* __restrict__ x, int ld, long n, int nc,
-                                   int64_t* __restrict__ cls, float* __restrict__ score) {
-  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  const float* row = x + (size_t)r * ld;
+// the first maximum of a row of logits and its float32 softmax value: the one definition
+// behind rg_softmax_max and rg_cluster_class_from_objects
+__device__ __forceinline__ void softmax_max_row(const float* __restrict__ row, int nc, int& am,
+                                                float& score) {
   float m = row[0];
-  int am = 0;
+  am = 0;
   for (int k = 1; k < nc; ++k)
     if (row[k] > m) {
       m = row[k];
@@ -176,8 +177,48 @@ __global__ void softmax_max_kernel(const float* __restrict__ x, int ld, long n, 
     }
   float s = 0.f;
   for (int k = 0; k < nc; ++k) s += expf(row[k] - m);
+  score = 1.f / s;
+}
+
+__global__ void softmax_max_kernel(const float* __restrict__ x, int ld, long n, int nc,
+                                   int64_t* __restrict__ cls, float* __restrict__ score) {
+  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  int am;
+  float s;
+  softmax_max_row(x + (size_t)r * ld, nc, am, s);
   if (cls) cls[r] = am;
-  if (score) score[r] = 1.f / s;
+  if (score) score[r] = s;
+}
+
+// ------------------------------------------------------------------ classifier classes
+// every cluster starts as one that no object names ...
+__global__ void class_fill_kernel(int ncl, int64_t fill, int64_t* __restrict__ cls,
+                                  float* __restrict__ score) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncl) return;
+  cls[c] = fill;
+  if (score) score[c] = 0.f;
+}
+
+// ... and, after it in stream order, object o writes the slot of its source cluster (the
+// entries of obj_cluster are distinct: one writer per slot)
+__global__ void class_scatter_kernel(const float* __restrict__ x, int ld, long n, int nc,
+                                     const int* __restrict__ obj_cluster, int ncl,
+                                     int64_t* __restrict__ cls, float* __restrict__ score,
+                                     int* __restrict__ bad) {
+  const long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= n) return;
+  const int c = obj_cluster[o];
+  if (c < 0 || c >= ncl) {
+    atomicExch(bad, 1);
+    return;
+  }
+  int am;
+  float s;
+  softmax_max_row(x + (size_t)o * ld, nc, am, s);
+  cls[c] = am;
+  if (score) score[c] = s;
 }
 
 // ------------------------------------------------------------------ selection
@@ -408,6 +449,33 @@ extern "C" int rg_softmax_max(const float* x, int ld, long n_rows, int num_class
              n_rows);
   softmax_max_kernel<<<ceil_div(n_rows, 256), 256, 0, (hipStream_t)stream>>>(x, ld, n_rows,
                                                                            num_classes, cls, score);
+  RG_LAUNCH_CHECK();
+  return RG_OK;
+}
+
+extern "C" int rg_cluster_class_from_objects(const float* logits, int ld, long n_objects,
+                                             int num_classes, const int* obj_cluster,
+                                             int n_clusters, int64_t fill_class,
+                                             int64_t* cluster_class, float* cluster_score,
+                                             int* bad_index, void* stream) {
+  RG_REQUIRE(n_objects >= 0 && n_clusters >= 0, RG_ERR_ARG,
+             "rg_cluster_class_from_objects: n_objects=%ld n_clusters=%d", n_objects, n_clusters);
+  RG_REQUIRE(num_classes >= 1 && num_classes <= MAXC, RG_ERR_UNSUPPORTED,
+             "rg_cluster_class_from_objects: num_classes=%d outside 1..%d", num_classes, MAXC);
+  RG_REQUIRE(ld >= num_classes, RG_ERR_ARG, "rg_cluster_class_from_objects: ld=%d < %d", ld,
+             num_classes);
+  if (n_clusters == 0) return RG_OK;
+  RG_REQUIRE(cluster_class, RG_ERR_ARG,
+             "rg_cluster_class_from_objects: cluster_class is null with n_clusters=%d", n_clusters);
+  RG_REQUIRE(n_objects == 0 || (logits && obj_cluster && bad_index), RG_ERR_ARG,
+             "rg_cluster_class_from_objects: null pointer with n_objects=%ld", n_objects);
+  class_fill_kernel<<<ceil_div(n_clusters, 256), 256, 0, (hipStream_t)stream>>>(
+      n_clusters, fill_class, cluster_class, cluster_score);
+  RG_LAUNCH_CHECK();
+  if (n_objects == 0) return RG_OK;
+  class_scatter_kernel<<<ceil_div(n_objects, 256), 256, 0, (hipStream_t)stream>>>(
+      logits, ld, n_objects, num_classes, obj_cluster, n_clusters, cluster_class, cluster_score,
+      bad_index);
   RG_LAUNCH_CHECK();
   return RG_OK;
 }

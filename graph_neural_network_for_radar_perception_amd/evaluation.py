@@ -14,6 +14,11 @@ for batches of frames:
   DetectionEvaluator                 performance_eval_detection.ipynb: confusion matrix,
                                      ground-truth and prediction counts, precision, recall
   SegmentationEvaluator              performance_eval_segmentation.ipynb: node-level confusion
+  ObjectClassEvaluator               the same matrix over proposals: predicted class against
+                                     the majority node class (datagen_classifier.py:50-60)
+  TwoStageEvaluators                 detection and object-level counts for the three class
+                                     sources (vote, object head, cluster-level classifier;
+                                     detection_accuracy.py:95-109) on one association
 
 The predicted node class is the argmax of the ``node_cls`` logits, lowest index on a tie.  The
 reference takes the argmax of the float32 softmax (detection_accuracy.py:97-98), which is the
@@ -444,8 +449,9 @@ class _Counters:
         if self._dev is None:
             self._dev = {k: torch.zeros(self._shape(k), dtype=torch.int64, device=dev)
                          for k in self.NAMES}
-            # [0]: a class id out of range, [1]: a centre that is not finite ('l2_norm')
-            self._bad = torch.zeros(2, dtype=torch.int32, device=dev)
+            # [0]: a class id out of range, [1]: a centre that is not finite ('l2_norm'),
+            # [2]: an index out of range in the object stage that fed the evaluator
+            self._bad = torch.zeros(3, dtype=torch.int32, device=dev)
         elif self._bad.device != dev:
             raise ValueError(f'evaluator lives on {self._bad.device}, update came from {dev}')
         return self._dev
@@ -456,11 +462,14 @@ class _Counters:
             torch = _torch()
             flat = torch.cat([self._dev[k].reshape(-1) for k in self.NAMES]
                              + [self._bad.to(torch.int64)]).cpu().numpy()
-            if flat[-2]:
+            if flat[-3]:
                 raise RuntimeError('a class id outside [0, num_classes) reached the evaluator')
-            if flat[-1]:
+            if flat[-2]:
                 raise RuntimeError("a cluster centre that is not finite reached the 'l2_norm' "
                                    'association (the reference raises on such a frame)')
+            if flat[-1]:
+                raise RuntimeError('a member, label or cluster index outside its range reached '
+                                   'the object stage that fed the evaluator')
             off = 0
             for k in self.NAMES:
                 n = int(np.prod(self._shape(k)))
@@ -500,14 +509,28 @@ class DetectionEvaluator(_Counters):
     the track keys, the predicted clusters' classes, the size filter, the greedy association
     (compute_gt_and_pred_associations) and the three count matrices.  association_criteria is
     the reference's: 'inv_iou' (1 - IoU of the member sets) or 'l2_norm' (the float32 distance
-    between the cluster centres, which needs the node positions: ``update(..., xy=)``)."""
+    between the cluster centres, which needs the node positions: ``update(..., xy=)``).
+
+    class_source names where a predicted cluster's class comes from (detection_accuracy.py:95-109
+    has the first two): 'segmentation' (the majority of its node classes), 'object_head' (the
+    detector's object head) or 'classifier' (the cluster-level classifier's class, handed to
+    ``update`` as ``cluster_class``).  None keeps ``by_segmentation``'s meaning."""
+
+    CLASS_SOURCES = ('segmentation', 'object_head', 'classifier')
 
     NAMES = ('confusion_matrix', 'gt_count_matrix', 'pred_count_matrix')
 
     def __init__(self, num_classes: int = 7, eps: float = 0.7, cluster_size_threshold: int = 0,
                  by_segmentation: bool = True, false_class_label: int = 6,
-                 association_criteria: str = 'inv_iou'):
+                 association_criteria: str = 'inv_iou', class_source: Optional[str] = None):
         super().__init__(num_classes)
+        if class_source is None:
+            class_source = 'segmentation' if by_segmentation else 'object_head'
+        elif class_source not in self.CLASS_SOURCES:
+            raise ValueError(f'class_source {class_source!r}: one of {self.CLASS_SOURCES}')
+        else:
+            by_segmentation = class_source == 'segmentation'
+        self.class_source = class_source
         if association_criteria not in ('inv_iou', 'l2_norm'):
             raise ValueError(f"association_criteria {association_criteria!r}: "
                              "'inv_iou' or 'l2_norm'")
@@ -521,8 +544,15 @@ class DetectionEvaluator(_Counters):
         self.by_segmentation = bool(by_segmentation)
         self.false_class_label = int(false_class_label)
 
+    def _association_params(self, N: int, F: int, ncl: int) -> dict:
+        """What two evaluators must agree on to share one batch's association."""
+        return dict(association_criteria=self.association_criteria, eps=self.eps,
+                    cluster_size_threshold=self.cluster_size_threshold, n_nodes=N, n_frames=F,
+                    n_clusters=ncl)
+
     def update(self, node_cls, obj_cls, pred_cluster_ptr, pred_cluster_idx, node_gt_class,
-               track_key, frame_ptr, max_frame_nodes: Optional[int] = None, xy=None):
+               track_key, frame_ptr, max_frame_nodes: Optional[int] = None, xy=None,
+               cluster_class=None, association: Optional[dict] = None):
         """One batch, every tensor on the device, no host synchronisation.  node_cls f32
         [N, C] logits, obj_cls f32 [clusters, C] logits (read only when not by_segmentation),
         pred_cluster_ptr / pred_cluster_idx the predicted clusters' CSR over global node ids
@@ -532,27 +562,54 @@ class DetectionEvaluator(_Counters):
         node positions, required under 'l2_norm' and ignored under 'inv_iou'.  ``self.last``
         keeps the batch's device tensors (ground-truth clusters, predicted classes, picks;
         under 'l2_norm' also the centres gt_mu / pred_mu by cluster id) until the next
-        update."""
+        update.
+
+        cluster_class int64 [clusters] on the device: the predicted clusters' classes under
+        class_source='classifier' (required there; neither node_cls' argmax nor obj_cls is
+        read), ignored otherwise.
+
+        association: the ``last`` of another DetectionEvaluator that was updated on this same
+        batch with the same criterion, eps and cluster_size_threshold (anything else is a
+        ValueError).  The association does not depend on the classes, so the ground-truth
+        clusters and the picks are taken from there and only the class source and the counts
+        are this evaluator's: several class sources cost one association per batch."""
         torch = _torch()
+        N, F = int(node_cls.shape[0]), int(frame_ptr.shape[0]) - 1
+        ncl = int(pred_cluster_ptr.numel()) - 1
+        by_classifier = self.class_source == 'classifier'
+        if by_classifier:
+            if cluster_class is None:
+                raise ValueError("class_source='classifier' needs the clusters' classes "
+                                 '(cluster_class)')
+            if int(cluster_class.numel()) < ncl:
+                raise ValueError(f'cluster_class has {cluster_class.numel()} entries for {ncl} '
+                                 'clusters')
+        if association is not None:
+            want = self._association_params(N, F, ncl)
+            have = association.get('params')
+            if have != want:
+                raise ValueError(f'association= comes from an update with {have}, this one is '
+                                 f'{want}: share an association only between evaluators updated '
+                                 'on the same batch with the same criterion, eps and '
+                                 'cluster_size_threshold')
         dev = node_cls.device
         if dev.type != 'cuda':
             raise ValueError('DetectionEvaluator.update needs device tensors')
         l2 = self.association_criteria == 'l2_norm'
-        if l2 and xy is None:
+        if l2 and xy is None and association is None:
             raise ValueError("association_criteria='l2_norm' needs the node positions (xy)")
         lib = nat.lib()
         st = nat.stream_ptr(dev)
         acc = self._device_counters(dev)
-        N, F = int(node_cls.shape[0]), int(frame_ptr.shape[0]) - 1
         if N == 0 or F <= 0:
             return self
         fptr = frame_ptr.to(torch.int32).contiguous()
-        gt = gt_clusters(track_key, node_gt_class, fptr, self._ws)
-        ncl = int(pred_cluster_ptr.numel()) - 1
         p_ptr = _full_ptr(pred_cluster_ptr, N)
         p_idx = pred_cluster_idx.to(torch.int32).contiguous()
-        p_of = cluster_of(p_ptr, p_idx, N)
-        if self.by_segmentation:
+        if by_classifier:
+            p_cls = (cluster_class.detach().to(dev, torch.int64).reshape(-1).contiguous()
+                     if ncl > 0 else torch.zeros(1, dtype=torch.int64, device=dev))
+        elif self.by_segmentation:
             node_pred = argmax_rows(node_cls)
             p_cls = torch.empty(max(ncl, 1), dtype=torch.int64, device=dev)
             nat.check(lib.rg_cluster_majority_label(node_pred.data_ptr(), p_ptr.data_ptr(),
@@ -564,20 +621,29 @@ class DetectionEvaluator(_Counters):
                 raise ValueError(f'obj_cls has {obj_cls.shape[0]} rows for {ncl} clusters')
             p_cls = argmax_rows(obj_cls) if ncl > 0 else torch.zeros(1, dtype=torch.int64,
                                                                      device=dev)
-        if l2:
-            if int(xy.shape[0]) != N:
-                raise ValueError(f'xy has {xy.shape[0]} rows for {N} nodes')
-            gt_mu = cluster_centres(xy, gt['cluster_ptr'], gt['cluster_idx'])
-            pred_mu = cluster_centres(xy, p_ptr, p_idx)
-            res = associate_l2(fptr, gt['cluster_ptr'], gt['cluster_idx'], p_ptr, p_idx, gt_mu,
-                               pred_mu, self.eps, self.cluster_size_threshold, max_frame_nodes,
-                               self._ws)
-            # the kernel sets, never clears: one flag serves every update
-            self._bad[1:].bitwise_or_(res['bad_value'])
+        gt_mu = pred_mu = None
+        if association is not None:
+            gt, res = association['gt'], association['assoc']
+            gt_mu, pred_mu = association.get('gt_mu'), association.get('pred_mu')
+            if 'bad_value' in res:
+                self._bad[1:2].bitwise_or_(res['bad_value'])
         else:
-            res = associate(fptr, gt['cluster_of'], gt['cluster_ptr'], gt['cluster_idx'], p_of,
-                            p_ptr, p_idx, self.eps, self.cluster_size_threshold, max_frame_nodes,
-                            self._ws)
+            gt = gt_clusters(track_key, node_gt_class, fptr, self._ws)
+            if l2:
+                if int(xy.shape[0]) != N:
+                    raise ValueError(f'xy has {xy.shape[0]} rows for {N} nodes')
+                gt_mu = cluster_centres(xy, gt['cluster_ptr'], gt['cluster_idx'])
+                pred_mu = cluster_centres(xy, p_ptr, p_idx)
+                res = associate_l2(fptr, gt['cluster_ptr'], gt['cluster_idx'], p_ptr, p_idx,
+                                   gt_mu, pred_mu, self.eps, self.cluster_size_threshold,
+                                   max_frame_nodes, self._ws)
+                # the kernel sets, never clears: one flag serves every update
+                self._bad[1:2].bitwise_or_(res['bad_value'])
+            else:
+                p_of = cluster_of(p_ptr, p_idx, N)
+                res = associate(fptr, gt['cluster_of'], gt['cluster_ptr'], gt['cluster_idx'],
+                                p_of, p_ptr, p_idx, self.eps, self.cluster_size_threshold,
+                                max_frame_nodes, self._ws)
         nat.check(lib.rg_eval_accumulate(
             res['pick_gt_cluster'].data_ptr(), res['pick_pred_cluster'].data_ptr(),
             res['pick_positive'].data_ptr(), res['gt_kept'].data_ptr(),
@@ -585,7 +651,8 @@ class DetectionEvaluator(_Counters):
             self.num_classes, self.false_class_label, acc['confusion_matrix'].data_ptr(),
             acc['gt_count_matrix'].data_ptr(), acc['pred_count_matrix'].data_ptr(),
             self._bad.data_ptr(), st), 'rg_eval_accumulate')
-        self.last = dict(gt=gt, pred_class=p_cls[:ncl], assoc=res)
+        self.last = dict(gt=gt, pred_class=p_cls[:ncl], assoc=res,
+                         params=self._association_params(N, F, ncl))
         if l2:
             self.last.update(gt_mu=gt_mu, pred_mu=pred_mu)
         return self
@@ -671,21 +738,194 @@ class SegmentationEvaluator(_Counters):
         return out
 
 
+class ObjectClassEvaluator(_Counters):
+    """The object-level confusion matrix of the two-stage flow: confusion[gt class, predicted
+    class] and gt_count over proposals, as SegmentationEvaluator keeps them over nodes.  The
+    ground truth of a proposal is its majority node class, lowest label on a tie
+    (datagen_classifier.py:50-60: what ``objects.classifier_inputs(node_labels=)`` returns as
+    ``object_class`` and what the classifier trains on)."""
+
+    NAMES = ('confusion_matrix', 'gt_count_matrix')
+
+    def __init__(self, num_classes: int = 7):
+        super().__init__(num_classes)
+
+    def update(self, pred_class, gt_class):
+        """pred_class and gt_class [rows] class ids on the device (rg_eval_class_confusion); no
+        host sync."""
+        torch = _torch()
+        dev = pred_class.device
+        if dev.type != 'cuda':
+            raise ValueError('ObjectClassEvaluator.update needs device tensors')
+        pred = pred_class.detach().to(torch.int64).reshape(-1).contiguous()
+        gt = gt_class.detach().to(dev, torch.int64).reshape(-1).contiguous()
+        if gt.numel() != pred.numel():
+            raise ValueError(f'{pred.numel()} predicted classes, {gt.numel()} ground-truth '
+                             'classes')
+        acc = self._device_counters(dev)
+        if pred.numel() > 0:
+            nat.check(nat.lib().rg_eval_class_confusion(
+                gt.data_ptr(), pred.data_ptr(), int(pred.numel()), self.num_classes,
+                acc['confusion_matrix'].data_ptr(), acc['gt_count_matrix'].data_ptr(),
+                self._bad.data_ptr(), nat.stream_ptr(dev)), 'rg_eval_class_confusion')
+        return self
+
+    def update_logits(self, logits, gt_class):
+        """logits f32 [rows, C] (the classifier's, one row per kept object): the predicted
+        class is ``argmax_rows``."""
+        x = _rows(logits)
+        if x.device.type != 'cuda':
+            raise ValueError('ObjectClassEvaluator.update_logits needs device tensors')
+        if int(x.shape[1]) != self.num_classes:
+            raise ValueError(f'logits have {x.shape[1]} classes, evaluator {self.num_classes}')
+        return self.update(argmax_rows(x), gt_class)
+
+    def result(self, invalid_class_index: Optional[int] = INVALID_CLS_IDX) -> dict:
+        out = self.counts()
+        out.update(segmentation_report(out['confusion_matrix'], out['gt_count_matrix'],
+                                       invalid_class_index))
+        return out
+
+
+class TwoStageEvaluators:
+    """The two-stage flow scored next to the single-stage class sources, on one association.
+
+    ``detection``: a DetectionEvaluator per class source ('segmentation', 'object_head',
+    'classifier'; detection_accuracy.py:95-109 with the classifier as the third) -- per batch
+    the first one associates, the other two accumulate on its picks
+    (``share_association=False``: each associates for itself; the counts are the same).
+    ``object_class``: an ObjectClassEvaluator per source over the proposals the classifier
+    keeps (size >= min_meas), so the vote and the head are scored on the classifier's objects.
+
+    The reference's detection evaluation keeps clusters of size > cluster_size_threshold, the
+    classifier sees those of size >= min_meas: the constructor wants cluster_size_threshold >=
+    min_meas - 1, so that every cluster the association keeps has a classifier class and no
+    fill value ever reaches a count matrix.  detection_kwargs are DetectionEvaluator's (eps,
+    cluster_size_threshold, false_class_label, association_criteria)."""
+
+    SOURCES = DetectionEvaluator.CLASS_SOURCES
+
+    def __init__(self, num_classes: int = 7, min_meas: int = 2, share_association: bool = True,
+                 **detection_kwargs):
+        for k in ('by_segmentation', 'class_source'):
+            if k in detection_kwargs:
+                raise ValueError(f'{k} is set per source by TwoStageEvaluators')
+        if int(min_meas) < 0:
+            raise ValueError(f'min_meas={min_meas} < 0')
+        thr = int(detection_kwargs.get('cluster_size_threshold', 0))
+        if thr < int(min_meas) - 1:
+            raise ValueError(f'cluster_size_threshold={thr} < min_meas - 1 = {int(min_meas) - 1}: '
+                             'the association would keep clusters the classifier never sees')
+        self.num_classes = int(num_classes)
+        self.min_meas = int(min_meas)
+        self.share_association = bool(share_association)
+        self.detection = {s: DetectionEvaluator(num_classes, class_source=s, **detection_kwargs)
+                          for s in self.SOURCES}
+        self.object_class = {s: ObjectClassEvaluator(num_classes) for s in self.SOURCES}
+
+    @property
+    def association_criteria(self) -> str:
+        return self.detection['segmentation'].association_criteria
+
+    def shares_with(self, other: DetectionEvaluator) -> bool:
+        """Whether ``other``'s association of a batch is the one these evaluators would make."""
+        d = self.detection['segmentation']
+        return (self.share_association and other.association_criteria == d.association_criteria
+                and other.eps == d.eps
+                and other.cluster_size_threshold == d.cluster_size_threshold)
+
+    def update(self, node_cls, obj_cls, pred_cluster_ptr, pred_cluster_idx, node_gt_class,
+               track_key, frame_ptr, classified: dict, max_frame_nodes: Optional[int] = None,
+               xy=None, association: Optional[dict] = None):
+        """One batch: DetectionEvaluator.update's arguments and ``classified``, the dict of
+        ``objects.classify_detections(..., node_labels=node_gt_class)`` on the same clusters.
+        ``association``: the ``last`` of a DetectionEvaluator already updated on this batch
+        with the same criterion, eps and threshold (``shares_with``), to associate not even
+        once here.  No host synchronisation."""
+        torch = _torch()
+        N, F = int(node_cls.shape[0]), int(frame_ptr.shape[0]) - 1
+        inp = classified['inputs']
+        if inp.object_class is None:
+            raise ValueError('classify_detections was run without node_labels: no ground truth '
+                             'per object')
+        if inp.min_meas != self.min_meas:
+            raise ValueError(f'the classifier kept proposals of size >= {inp.min_meas}, these '
+                             f'evaluators were built for min_meas={self.min_meas}')
+        if N == 0 or F <= 0:
+            return self
+        ccls = classified['cluster_class']
+        for s in self.SOURCES:
+            self.detection[s].update(node_cls, obj_cls, pred_cluster_ptr, pred_cluster_idx,
+                                     node_gt_class, track_key, frame_ptr,
+                                     max_frame_nodes=max_frame_nodes, xy=xy, cluster_class=ccls,
+                                     association=association)
+            if self.share_association and association is None:
+                association = self.detection[s].last
+        clf = self.object_class['classifier']
+        clf._device_counters(node_cls.device)
+        clf._bad[2:3].bitwise_or_(classified['bad'])
+        if inp.n_objects == 0:
+            return self
+        oc = inp.object_cluster.to(torch.int64)
+        clf.update_logits(classified['logits'], inp.object_class)
+        for s in ('segmentation', 'object_head'):
+            pred = self.detection[s].last['pred_class'].index_select(0, oc)
+            self.object_class[s].update(pred, inp.object_class)
+        return self
+
+    def merge(self, other):
+        """Add another TwoStageEvaluators' counters (another rank's, another sequence's)."""
+        if type(other) is not type(self) or other.num_classes != self.num_classes \
+                or other.min_meas != self.min_meas:
+            raise ValueError('merge needs TwoStageEvaluators of the same num_classes and '
+                             'min_meas')
+        for s in self.SOURCES:
+            self.detection[s].merge(other.detection[s])
+            self.object_class[s].merge(other.object_class[s])
+        return self
+
+    def result(self, invalid_class_index: Optional[int] = INVALID_CLS_IDX) -> dict:
+        """One dict per source: {'detection': DetectionEvaluator.result(), 'object_class':
+        ObjectClassEvaluator.result()}."""
+        return {s: dict(detection=self.detection[s].result(invalid_class_index),
+                        object_class=self.object_class[s].result(invalid_class_index))
+                for s in self.SOURCES}
+
+    def to_json(self, prefix, class_names) -> dict:
+        """The reference's per-sequence files, two per source: ``<prefix>_<source>_detection
+        .json`` and ``<prefix>_<source>_object_class.json``."""
+        return {s: dict(
+            detection=self.detection[s].to_json(f'{prefix}_{s}_detection.json', class_names),
+            object_class=self.object_class[s].to_json(f'{prefix}_{s}_object_class.json',
+                                                      class_names))
+            for s in self.SOURCES}
+
+
 # ------------------------------------------------------------------------- a whole sequence
 def evaluate_window_batch(win, model, cfg, detection: Optional[DetectionEvaluator] = None,
                           segmentation: Optional[SegmentationEvaluator] = None,
                           dtype: str = 'fp32', reject_outlier_by_ransac: bool = False,
-                          cache: Optional[dict] = None):
+                          cache: Optional[dict] = None, classifier=None,
+                          two_stage: Optional[TwoStageEvaluators] = None, meas_noise_cov=None):
     """One batch of windows (a batch ``frontend.ScanWindow``) through the front-end, the graph
     build, the detector's proposal forward and the evaluators' ``update``: what the notebooks
     do per frame (performance_eval_detection.ipynb, performance_eval_segmentation.ipynb),
     for every window of the batch at once.  ``model`` is a ``Model_Inference`` with its
     proposal parameters set; ``cache`` keeps workspaces and buffers between batches.  Returns
     the batch's FrameBatch (``frontend.frame_batch``) and the forward's outputs (None for a
-    batch without a frame of more than one node)."""
+    batch without a frame of more than one node).
+
+    With ``classifier`` (the cluster-level classifier's model; ``two_stage`` is then required)
+    the batch also runs ``objects.classify_detections`` with the ground-truth node classes
+    (``two_stage.min_meas``; ``meas_noise_cov`` defaults to the detector's) and updates
+    ``two_stage``, on ``detection``'s association where ``two_stage.shares_with(detection)``.
+    The one host read that adds is ``objects.classifier_inputs``'.  Without a classifier
+    nothing of this runs."""
     from . import frontend, objects
     if not getattr(model, 'extract_proposals', False):
         raise ValueError('the detector has no proposal branch: set_param_for_proposal_extraction')
+    if classifier is not None and two_stage is None:
+        raise ValueError('a classifier needs the evaluators it updates (two_stage)')
     cache = cache if cache is not None else {}
     dd, gd = frontend.dynamic_frame(win, reject_outlier_by_ransac, with_keys=True)
     fb = frontend.frame_batch(dd, gd)
@@ -700,28 +940,59 @@ def evaluate_window_batch(win, model, cfg, detection: Optional[DetectionEvaluato
                          fb.track_key, fb.frame_ptr, max_frame_nodes=max(fb.frame_sizes), xy=xy)
     if segmentation is not None:
         segmentation.update(out.node_cls, gt_class)
+    if classifier is not None:
+        res = objects.classify_detections(det, classifier, two_stage.min_meas, meas_noise_cov,
+                                          node_labels=gt_class,
+                                          num_classes=two_stage.num_classes)
+        shared = None
+        if detection is not None and fb.n_nodes > 0 and two_stage.shares_with(detection):
+            shared = detection.last
+        xy = det.xy if two_stage.association_criteria == 'l2_norm' else None
+        two_stage.update(out.node_cls, out.obj_cls, out.cluster_ptr, out.cluster_idx, gt_class,
+                         fb.track_key, fb.frame_ptr, res, max_frame_nodes=max(fb.frame_sizes),
+                         xy=xy, association=shared)
     return fb, out
 
 
 def evaluate_sequence(store, model, cfg, window_size: int = 10, batch_windows: int = 64,
                       dtype: str = 'fp32', detection: Optional[DetectionEvaluator] = None,
                       segmentation: Optional[SegmentationEvaluator] = None,
-                      reject_outlier_by_ransac: bool = False):
+                      reject_outlier_by_ransac: bool = False, classifier=None,
+                      two_stage: Optional[TwoStageEvaluators] = None, meas_noise_cov=None):
     """Every sliding window of a ``sequence.SequenceStore`` to the notebooks' count matrices:
     per batch of ``batch_windows`` consecutive sliding positions ``store.windows`` ->
     ``evaluate_window_batch``.  No host work per window; per batch the host waits only where
     ``frontend.select_dynamic`` and ``engine.propose_clusters`` already do and for the one
     ``frame_ptr`` read of ``frontend.frame_batch``.  Returns (detection, segmentation), new
-    evaluators unless given; their ``result()`` is the only read of the counters."""
+    evaluators unless given; their ``result()`` is the only read of the counters.
+
+    With ``classifier`` every batch also goes through the second stage and the return is
+    (detection, segmentation, two_stage): ``two_stage`` a TwoStageEvaluators, by default of
+    min_meas = 2 with ``detection``'s eps and criterion and its cluster_size_threshold raised
+    to at least 1 (the least the constructor accepts for min_meas = 2).  Per batch the host
+    waits once more, in ``objects.classifier_inputs``."""
     if int(batch_windows) < 1:
         raise ValueError(f'batch_windows={batch_windows} < 1')
     detection = detection if detection is not None else DetectionEvaluator(int(cfg.num_classes))
     segmentation = (segmentation if segmentation is not None
                     else SegmentationEvaluator(int(cfg.num_classes)))
+    if classifier is not None and two_stage is None:
+        two_stage = TwoStageEvaluators(
+            detection.num_classes, min_meas=2, eps=detection.eps,
+            cluster_size_threshold=max(detection.cluster_size_threshold, 1),
+            false_class_label=detection.false_class_label,
+            association_criteria=detection.association_criteria)
     n = store.n_windows(window_size)
     cache: dict = {}
     for i0 in range(0, n, int(batch_windows)):
         win = store.windows(range(i0, min(i0 + int(batch_windows), n)), window_size)
-        evaluate_window_batch(win, model, cfg, detection, segmentation, dtype,
-                              reject_outlier_by_ransac, cache)
-    return detection, segmentation
+        if classifier is None:
+            evaluate_window_batch(win, model, cfg, detection, segmentation, dtype,
+                                  reject_outlier_by_ransac, cache)
+        else:
+            evaluate_window_batch(win, model, cfg, detection, segmentation, dtype,
+                                  reject_outlier_by_ransac, cache, classifier, two_stage,
+                                  meas_noise_cov)
+    if classifier is None:
+        return detection, segmentation
+    return detection, segmentation, two_stage

@@ -9,6 +9,8 @@ list and to the cluster-level classifier's inputs, for a batch of frames, with n
   object_list          the numbers of process_frame (modules/inference/output.py:99-171)
   compute_proposals, compute_cov_ellipse    drop-ins with the reference's signatures
   detect, classify_proposals, classifier_training_batch    the two-stage glue
+  classify_detections, cluster_class_from_objects    the classifier as a class source per
+                       proposal cluster (output.py:111-128 with the second stage's class)
 
 Everything works on global node ids, ``frame_ptr`` int32 [F + 1] and clusters as the CSR that
 ``engine.propose_clusters`` returns.  Kernels are enqueued on the current stream.
@@ -193,6 +195,44 @@ def majority_class(node_class, cluster_ptr, cluster_idx, num_classes: int, bad=N
     return out
 
 
+def cluster_class_from_objects(logits, object_cluster, n_clusters: int, fill_class: int,
+                               bad=None):
+    """(class int64 [K], score f32 [K]) of the K = n_clusters proposal clusters from the
+    cluster-level classifier's logits f32 [K', classes] per kept object and object_cluster int32
+    [K'] (ClassifierInputs.object_cluster): ``softmax_max`` of every row, bit for bit, at the
+    slot of its source cluster; ``fill_class`` and 0.0 for a cluster that no object names
+    (rg_cluster_class_from_objects).  No synchronisation: an object_cluster entry outside
+    [0, K) sets ``bad`` (int32 [1] on the device, the stage's ``stats['bad']``; a private flag
+    when None) and writes nothing."""
+    torch = _torch()
+    x = logits.detach()
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    if x.dim() != 2:
+        raise ValueError(f'expected a [objects, classes] matrix, got {tuple(x.shape)}')
+    n, nc, K = int(x.shape[0]), int(x.shape[1]), int(n_clusters)
+    if not 1 <= nc <= 32:
+        raise ValueError(f'num_classes={nc} outside 1..32')
+    if K < 0:
+        raise ValueError(f'n_clusters={n_clusters} < 0')
+    if int(object_cluster.numel()) != n:
+        raise ValueError(f'{object_cluster.numel()} source clusters for {n} objects')
+    if n > 0 and x.stride(1) != 1:
+        x = x.contiguous()
+    dev = x.device
+    oc = _i32(object_cluster.to(dev))
+    cls = _empty(dev, K, torch.int64)
+    score = _empty(dev, K, torch.float32)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if K > 0:
+        nat.check(nat.lib().rg_cluster_class_from_objects(
+            x.data_ptr(), int(x.stride(0)) if n > 0 else nc, n, nc, oc.data_ptr(), K,
+            int(fill_class), cls.data_ptr(), score.data_ptr(), bad.data_ptr(),
+            nat.stream_ptr(dev)), 'rg_cluster_class_from_objects')
+    return cls, score
+
+
 def _select(ptr, idx, fptr, F, cls, num_classes, min_meas, drop_class):
     """rg_object_select: device tensors sized by the cluster count (no synchronisation)."""
     torch = _torch()
@@ -244,7 +284,8 @@ class ClassifierInputs:
     without labels), object_mu f32 [K', 2], object_sigma f32 [K', 2, 2], object_cluster int32
     [K'] (the source cluster of every kept object), object_frame int32 [K'], frame_obj_ptr /
     frame_row_ptr int32 [F + 1] (each frame's range of objects / feature rows); n_objects,
-    n_rows, n_edges and max_size (the largest kept object; 0 with none) are host integers."""
+    n_rows, n_edges, max_size (the largest kept object; 0 with none) and min_meas (the size
+    threshold the objects were kept by) are host integers."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -345,7 +386,8 @@ def classifier_inputs(xy, rcs, cluster_ptr, cluster_idx, frame_ptr=None, meas_no
         object_sigma=obj['sigma'][:Kp], object_cluster=sel['obj_cluster'][:Kp],
         object_frame=obj['frame'][:Kp], obj_row_ptr=sel['obj_row_ptr'][:Kp + 1],
         frame_obj_ptr=sel['frame_obj_ptr'], frame_row_ptr=sel['frame_row_ptr'], n_objects=Kp,
-        n_rows=Mp, n_edges=Ep, n_frames=F, max_size=max_size, stats=stats)
+        n_rows=Mp, n_edges=Ep, n_frames=F, max_size=max_size, stats=stats,
+        min_meas=int(min_meas))
 
 
 # ---------------------------------------------------------------- object list
@@ -413,11 +455,18 @@ class ObjectList:
 def object_list(node_cls, link_cls, obj_cls, xy, cluster_ptr, cluster_idx, frame_ptr=None,
                 meas_noise_cov=None, detect_object_by_segmentation_output: bool = True,
                 false_class: Optional[int] = None, chi_sq: float = 2, n_points: int = 100,
-                points: bool = True, centres=None) -> ObjectList:
+                points: bool = True, centres=None, cluster_class=None,
+                cluster_score=None) -> ObjectList:
     """process_frame (output.py:99-171) for a batch: node / link class and score (max of the
     float32 softmax), the object class by the majority of the node classes or by the object
     head, the false-class filter (num_classes - 1), and size, mean, covariance and ellipse of
-    the remaining objects.  No synchronisation here."""
+    the remaining objects.  No synchronisation here.
+
+    ``cluster_class`` (int64 [K], on the device) is the third class source and takes precedence
+    over both: the classes of the cluster-level classifier as ``cluster_class_from_objects``
+    scatters them (output.py:111-128 with the second stage's class), ``cluster_score`` (f32 [K],
+    optional) their scores.  A proposal the classifier never saw carries the false class there,
+    so the filter drops it."""
     torch = _torch()
     xy = _xy(xy)
     dev = xy.device
@@ -432,7 +481,17 @@ def object_list(node_cls, link_cls, obj_cls, xy, cluster_ptr, cluster_idx, frame
     if link_cls is not None:
         link_class, link_score = softmax_max(link_cls)
     stats = cluster_stats(xy, ptr, idx, meas_noise_cov)
-    if detect_object_by_segmentation_output:
+    if cluster_class is not None:
+        if int(cluster_class.numel()) < K:
+            raise ValueError(f'cluster_class has {cluster_class.numel()} entries for {K} clusters')
+        ccls = cluster_class.detach().to(dev, torch.int64).reshape(-1)[:K].contiguous()
+        cscore = None
+        if cluster_score is not None:
+            if int(cluster_score.numel()) < K:
+                raise ValueError(f'cluster_score has {cluster_score.numel()} entries for {K} '
+                                 'clusters')
+            cscore = cluster_score.detach().to(dev, torch.float32).reshape(-1)[:K].contiguous()
+    elif detect_object_by_segmentation_output:
         ccls, cscore = majority_class(node_class, ptr, idx, nc, stats['bad']), None
     else:
         if int(obj_cls.shape[0]) < K:
@@ -597,8 +656,16 @@ def detect_frames(detector, fb, cfg, dtype: str = 'fp32', cache: Optional[dict] 
 
 
 def detections_object_list(det: Detections, detect_object_by_segmentation_output: bool = True,
+                           classifier=None, min_meas: Optional[int] = None,
                            **kw) -> ObjectList:
-    """object_list of a detect() result."""
+    """object_list of a detect() result.  With ``classifier`` (the cluster-level classifier's
+    model) the object classes and scores are the second stage's: ``classify_detections`` with
+    ``min_meas``, its cluster_class / cluster_score handed to ``object_list`` -- a proposal
+    below min_meas, or one the classifier calls false, is no object."""
+    if classifier is not None:
+        res = classify_detections(det, classifier, min_meas,
+                                  num_classes=int(det.node_cls.shape[1]))
+        kw = dict(kw, cluster_class=res['cluster_class'], cluster_score=res['cluster_score'])
     return object_list(det.node_cls, det.link_cls, det.obj_cls, det.xy, det.cluster_ptr,
                        det.cluster_idx, det.frame_ptr, det.meas_noise_cov,
                        detect_object_by_segmentation_output, centres=det.centres, **kw)
@@ -617,6 +684,35 @@ def classify_inputs(classifier_model, inp: ClassifierInputs):
     with torch.no_grad():
         return ce.forward_objects(model, inp.object_features, inp.object_num_meas, begin, end,
                                   model.compute_dtype, n_nodes=inp.n_rows, n_edges=inp.n_edges)
+
+
+def classify_detections(det, classifier_model, min_meas: Optional[int] = None,
+                        meas_noise_cov=None, node_labels=None, num_classes: int = 7) -> dict:
+    """The second stage of the two-stage flow for any ``Detections`` (``detect``,
+    ``detect_frames``): classifier inputs -> classifier forward -> a class and a score per
+    proposal cluster.  Returns the dict of ``classify_proposals`` (logits f32 [K', classes] per
+    kept object, object_cluster, object_frame, ``inputs``, ``detections``) plus cluster_class
+    int64 [K] / cluster_score f32 [K] over ALL proposal clusters (``cluster_class_from_objects``;
+    a cluster below min_meas carries num_classes - 1, the false class, and score 0: it is no
+    object of the two-stage flow, output.py:123-128 drops it) and ``bad`` (the stage's int32
+    flag, also set by an object_cluster entry out of range).  With ``node_labels`` [N]
+    ``inputs.object_class`` is every kept object's majority ground-truth class, lowest label on
+    a tie (datagen_classifier.py:50-60).  min_meas defaults to 2.  The one host read is
+    ``classifier_inputs``'."""
+    noise = det.meas_noise_cov if meas_noise_cov is None else meas_noise_cov
+    inp = classifier_inputs(det.xy, det.rcs, det.cluster_ptr, det.cluster_idx, det.frame_ptr,
+                            noise, 2 if min_meas is None else min_meas, node_labels=node_labels,
+                            num_classes=num_classes)
+    logits = classify_inputs(classifier_model, inp)
+    if int(logits.shape[1]) != int(num_classes):
+        raise ValueError(f'the classifier has {logits.shape[1]} classes, num_classes='
+                         f'{num_classes}')
+    K = int(det.cluster_ptr.numel()) - 1
+    bad = inp.stats['bad']
+    ccls, cscore = cluster_class_from_objects(logits, inp.object_cluster, K,
+                                              int(num_classes) - 1, bad)
+    return dict(logits=logits, object_cluster=inp.object_cluster, object_frame=inp.object_frame,
+                inputs=inp, detections=det, cluster_class=ccls, cluster_score=cscore, bad=bad)
 
 
 def classify_proposals(detector, classifier_model, node_features, edge_features, edge_index,

@@ -1128,6 +1128,15 @@ int rg_eval_node_confusion(const float* node_logits, int ld, const int64_t* node
                            long n_nodes, int num_classes, int64_t* confusion, int64_t* gt_count,
                            int* bad_class, void* stream);
 
+/* rg_eval_node_confusion for predictions that are class ids already (a cluster's majority
+ * class, the classes of rg_cluster_class_from_objects): confusion[gt_class[r]][pred_class[r]]
+ * += 1 and gt_count[gt_class[r]] += 1 over the n rows; accumulators as above.  A row with
+ * either class outside [0, num_classes) sets *bad_class (device int32, caller-zeroed) and is
+ * skipped.  num_classes outside 1..32: RG_ERR_UNSUPPORTED; n < 0: RG_ERR_ARG. */
+int rg_eval_class_confusion(const int64_t* gt_class, const int64_t* pred_class, long n,
+                            int num_classes, int64_t* confusion, int64_t* gt_count,
+                            int* bad_class, void* stream);
+
 /* ------------------------------------------------------------------ object stage */
 /* From the detector's clusters to the classifier's inputs and the object list
  * (modules/inference/inference.py, ellipse.py, output.py:99-171,
@@ -1161,6 +1170,22 @@ int rg_cov_ellipse(const float* eigval, const float* eigvec, const float* mu, in
  * (either nullable).  num_classes outside 1..32: RG_ERR_UNSUPPORTED. */
 int rg_softmax_max(const float* x, int ld, long n_rows, int num_classes, int64_t* cls,
                    float* score, void* stream);
+
+/* The cluster-level classifier as a class source per cluster (the object class of
+ * output.py:111-128, detection_accuracy.py:95-109, from the second stage): logits f32
+ * [n_objects][ld] per kept object, obj_cluster int32 [n_objects] the source cluster of every
+ * object (rg_object_select's).  cluster_class[obj_cluster[o]] / cluster_score[obj_cluster[o]]
+ * (nullable) = what rg_softmax_max returns for row o, bit for bit (one device function); a
+ * cluster that no object names gets fill_class and 0.0f.  A fill launch, then a scatter launch
+ * in stream order.  The entries of obj_cluster are distinct; duplicates are outside the
+ * domain (the last writer is not defined).  An entry outside [0, n_clusters) sets *bad_index
+ * (device int32, caller-zeroed) and writes nothing for that object.  n_objects == 0 still
+ * fills; n_clusters == 0 launches nothing.  num_classes outside 1..32: RG_ERR_UNSUPPORTED;
+ * ld < num_classes or a negative count: RG_ERR_ARG. */
+int rg_cluster_class_from_objects(const float* logits, int ld, long n_objects, int num_classes,
+                                  const int* obj_cluster, int n_clusters, int64_t fill_class,
+                                  int64_t* cluster_class, float* cluster_score, int* bad_index,
+                                  void* stream);
 
 /* remove_low_quality_proposals (datagen_classifier.py:166-190: kept when size >= min_meas) and
  * the class filter of output.py:123-128 (cluster_class[c] == drop_class is dropped; -1 = no
