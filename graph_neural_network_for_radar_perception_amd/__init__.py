@@ -5,6 +5,8 @@ Drop-in entry points (same names / signatures as the reference):
   gnn_detector.Model_Inference, gnn_detector.Model_Training,
   gnn_detector.Model_Object_Classifier_Finetuning              (gnn_detector.py)
   loss.Loss_Graph, loss.Loss_Object_Class                      (loss.py)
+  gnn_detector.Model_Inference_v2 (the GATv2 attention detector, forward only, fp32),
+  gnn_attention.residual_graph_attn_block, graph_attention, GATv2Conv  (gnn_attention.py)
   gnn_blocks.*, common.*                                       (gnn_blocks.py, common.py)
   graph_features.compute_adjacency_information / _v2,
   compute_node_features, compute_edge_features                 (graph_features.py)

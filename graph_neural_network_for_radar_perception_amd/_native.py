@@ -240,6 +240,11 @@ _SIGNATURES = {
     'rg_conv_wave_nodes': (_I, [_P, _I, _I, _P, _P]),
     'rg_conv_layer_fused_waves': (_I, [ctypes.POINTER(rg_layer), ctypes.POINTER(rg_layer), _I, _P,
                                        _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P]),
+    # graph attention (attention.hip)
+    'rg_linear_f32': (_I, [_P, _I, _P, _I, _I, _I, _P, _I, _L, _P, _P, _I, _P]),
+    'rg_gat_v2_layer_workspace_size': (_S, [_L, _I]),
+    'rg_gat_v2_layer': (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _L, _P, _I, _P, _P, _I, _I, _I, _F,
+                             _P, _I, _P, _S, _P]),
     'rg_cluster_majority_label': (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     'rg_cross_entropy': (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
     'rg_cross_entropy_backward': (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _P]),

@@ -112,6 +112,9 @@ class config:
         self.graph_convolution_stem_channels = list(arch['graph_convolution_stem_channels'])
         self.msg_mlp_hidden_dim = arch['msg_mlp_hidden_dim']
         self.num_blocks_to_compute_edge = arch['num_blocks_to_compute_edge']
+        # read by Model_Inference_v2 (gnn_detector.py:331-332)
+        self.hidden_node_channels_GAT = arch['hidden_node_channels_GAT']
+        self.num_heads_GAT = arch['num_heads_GAT']
         self.link_pred_stem_channels = list(arch['link_pred_stem_channels'])
         self.node_pred_stem_channels = list(arch['node_pred_stem_channels'])
         self.input_node_feat_dim = len(arch['node_features'])

@@ -9,6 +9,8 @@ library's):
                   weights; repacked automatically when a parameter changes
   ModelPlans      every chain of one Model_Inference (encoders, per-layer message /
                   update / residual chains, head chains) for one dtype
+  AttnPlan        one residual_graph_attn_block (Model_Inference_v2): the fused GATv2 layer
+                  (rg_gat_v2_layer) or the composed one, rg_linear_f32 for its wide linears
   DeviceGraph     destination-major CSR + link pairs of a batch of frames
   forward_batched the L-layer message passing and the four heads over a DeviceGraph
                   (Model_Inference.forward, gnn_detector.py:141-201, for many frames
@@ -1174,6 +1176,232 @@ class ConvPlan:
         return True
 
 
+# --------------------------------------------------------------------------- graph attention
+def linear_f32(weight: torch.Tensor, bias: Optional[torch.Tensor], x: torch.Tensor,
+               out: torch.Tensor, act: str = 'none', rows: Optional[int] = None, rows_dev=None):
+    """out[r] = act(x[r] W^T + b) for one nn.Linear of any width (rg_linear_f32: exact f32
+    products, weights read from the float32 parameter where it lies -- no packed image, so
+    nothing to keep in step with the parameter).  x, out: float32 rows (column slices of a
+    wider buffer are fine); rows_dev: optional device int32 row count."""
+    w = weight.detach()
+    b = bias.detach() if bias is not None else None
+    for t, what in ((w, 'weight'), (b, 'bias'), (x, 'input'), (out, 'output')):
+        if t is None:
+            continue
+        _require_device(t, what)
+        if t.dtype != torch.float32 or (t.dim() == 2 and t.stride(1) != 1) or \
+                (t.dim() == 1 and t.stride(0) != 1):
+            raise TypeError(f'linear_f32: {what} must be float32 with unit column stride')
+    if x.shape[1] != w.shape[1] or out.shape[1] != w.shape[0]:
+        raise ValueError(f'linear_f32: {tuple(x.shape)} rows through a {tuple(w.shape)} weight '
+                         f'into {tuple(out.shape)}')
+    n = int(x.shape[0] if rows is None else rows)
+    nat.check(nat.lib().rg_linear_f32(w.data_ptr(), w.stride(0), nat.ptr(b), w.shape[1], w.shape[0],
+                                      nat.ACT[act], x.data_ptr(), x.stride(0), n,
+                                      nat.ptr(rows_dev), out.data_ptr(), out.stride(0),
+                                      nat.stream_ptr(x.device)), 'rg_linear_f32')
+    return out
+
+
+def _edge_count(g: 'DeviceGraph') -> int:
+    """The graph's edge count on the host (one device read, kept, for a capacity-padded graph)."""
+    n = g.n_edges
+    if n is None:
+        n = getattr(g, '_n_edges_host', None)
+        if n is None:
+            n = g._n_edges_host = int(g.seg_ptr[g.n_nodes].item())
+    return min(int(n), int(g.n_edges_cap))
+
+
+def gat_fused_shape(gat) -> bool:
+    """Whether rg_gat_v2_layer is compiled for this GATv2Conv (the yml shape)."""
+    return gat.heads == 8 and gat.out_channels == 64 and gat.edge_dim == 64
+
+
+def gat_project(gat, x: torch.Tensor, xlr: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """xl | xr = lin_l(x) | lin_r(x) as one float32 [N][2 H C] buffer."""
+    HC = gat.heads * gat.out_channels
+    if xlr is None:
+        xlr = torch.empty((x.shape[0], 2 * HC), dtype=torch.float32, device=x.device)
+    linear_f32(gat.lin_l.weight, gat.lin_l.bias, x, xlr[:, :HC])
+    linear_f32(gat.lin_r.weight, gat.lin_r.bias, x, xlr[:, HC:])
+    return xlr
+
+
+def gat_fused(gat, xlr: torch.Tensor, e: torch.Tensor, g: 'DeviceGraph', out: torch.Tensor,
+              ws_cache: Optional[dict] = None) -> bool:
+    """The attention and aggregation of one GATv2Conv in rg_gat_v2_layer (two launches, the
+    logits [E_cap][H] the only per-edge buffer); False when the kernel is not compiled for
+    the shape (the caller then runs gat_composed)."""
+    lib = nat.lib()
+    dev = xlr.device
+    cap = int(g.n_edges_cap)
+    wsz = lib.rg_gat_v2_layer_workspace_size(cap, gat.heads)
+    ws = _workspace(ws_cache if ws_cache is not None else {}, 'gat_logits', wsz, dev)
+    w = gat.lin_edge.weight.detach()
+    rc = lib.rg_gat_v2_layer(
+        xlr.data_ptr(), xlr.stride(0), e.data_ptr(), e.stride(0), g.seg_ptr.data_ptr(),
+        g.src.data_ptr(), g.dst.data_ptr(), g.n_nodes, cap, w.data_ptr(), w.stride(0),
+        gat.att.detach().data_ptr(), gat.bias.detach().data_ptr(), gat.edge_dim, gat.heads,
+        gat.out_channels, float(gat.negative_slope), out.data_ptr(), out.stride(0), ws.data_ptr(),
+        wsz, nat.stream_ptr(dev))
+    if rc == nat.RG_ERR_UNSUPPORTED:
+        return False
+    nat.check(rc, 'rg_gat_v2_layer')
+    return True
+
+
+def gat_composed(gat, xlr: torch.Tensor, e: torch.Tensor, g: 'DeviceGraph', out: torch.Tensor):
+    """The same operator from the existing pieces, for every shape the fused kernel is not
+    compiled for and as the benchmark's baseline: rg_linear_f32 for lin_edge, rg_segment_reduce
+    ('max', then 'add') for the softmax and the weighted sum, torch elementwise operators in
+    between.  It MATERIALISES the E x H C tensors (e W_e^T, the gathered sum, the weighted
+    rows) that the fused kernel never writes -- the path a caller had to write."""
+    H, C = gat.heads, gat.out_channels
+    HC = H * C
+    if HC % 4:
+        raise NotImplementedError(f'graph attention: heads x channels = {HC} is not a multiple '
+                                  'of 4 (rg_segment_reduce reduces 16-byte row pieces)')
+    N = g.n_nodes
+    E = _edge_count(g)
+    dev = xlr.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    bias = gat.bias.detach()
+    if E == 0 or N == 0:
+        out.copy_(bias.expand(N, HC))
+        return out
+    src, dst = g.src[:E].long(), g.dst[:E].long()
+    xl, xr = xlr[:, :HC], xlr[:, HC:]
+    m = torch.empty((E, HC), **f32)
+    linear_f32(gat.lin_edge.weight, None, e, m, rows=E)
+    xj = xl[src]                                                     # [E, H C]
+    m += xj
+    m += xr[dst]
+    att = gat.att.detach().reshape(1, H, C)
+    Hp = (H + 3) // 4 * 4
+    a = torch.zeros((E, Hp), **f32)
+    a[:, :H] = (torch.nn.functional.leaky_relu(m, gat.negative_slope).view(E, H, C) * att).sum(-1)
+    amax = torch.empty((N, Hp), **f32)
+    segment_reduce(a, g.seg_ptr, N, 'max', amax)
+    p = torch.exp(a - amax[dst])
+    den = torch.empty((N, Hp), **f32)
+    segment_reduce(p, g.seg_ptr, N, 'add', den)
+    wgt = (p / (den[dst] + 1e-16))[:, :H]
+    msg = (xj.view(E, H, C) * wgt.unsqueeze(-1)).view(E, HC)
+    agg = out if out.data_ptr() % 16 == 0 and out.stride(0) % 4 == 0 else torch.empty((N, HC), **f32)
+    for c0 in range(0, HC, 256):   # rg_segment_reduce: up to 256 channels a call
+        c1 = min(c0 + 256, HC)
+        segment_reduce(msg[:, c0:c1], g.seg_ptr, N, 'add', agg[:, c0:c1])
+    if agg is not out:
+        out.copy_(agg)   # (plumbing: unaligned columns of a wider buffer)
+    out += bias
+    return out
+
+
+def gat_v2_conv(gat, x: torch.Tensor, e: torch.Tensor, g: 'DeviceGraph',
+                out: Optional[torch.Tensor] = None, fused: Optional[bool] = None,
+                ws_cache: Optional[dict] = None) -> torch.Tensor:
+    """GATv2Conv.forward over a DeviceGraph: x float32 [N, in], e float32 [E_cap, edge_dim] in
+    destination-major order -> float32 [N, H C].  fused None: the fused kernel when it is
+    compiled for the shape, else the composed path; True: the fused kernel or an error;
+    False: the composed path."""
+    _require_device(x, 'node_features')
+    HC = gat.heads * gat.out_channels
+    with torch.no_grad():
+        xlr = gat_project(gat, x)
+        if out is None:
+            out = torch.empty((x.shape[0], HC), dtype=torch.float32, device=x.device)
+        aligned = out.data_ptr() % 16 == 0 and out.stride(0) % 4 == 0
+        dst = out if aligned else torch.empty((x.shape[0], HC), dtype=torch.float32,
+                                              device=x.device)
+        done = fused is not False and gat_fused_shape(gat) and gat_fused(gat, xlr, e, g, dst,
+                                                                         ws_cache)
+        if done and dst is not out:
+            out.copy_(dst)   # (plumbing: unaligned columns of a wider buffer)
+        if not done:
+            if fused:
+                raise RuntimeError('graph attention: rg_gat_v2_layer is not compiled for '
+                                   f'heads={gat.heads}, channels={gat.out_channels}, '
+                                   f'edge_dim={gat.edge_dim}')
+            gat_composed(gat, xlr, e, g, out)
+    return out
+
+
+class AttnPlan:
+    """One residual_graph_attn_block (gnn_attention.py:13-76) on the device, fp32:
+    GATv2Conv (gat_v2_conv), the first update layer over cat(x, [extra,] attention output) as
+    one rg_linear_f32 (its input is wider than the chain kernels' 256 features), the remaining
+    update layers as a chain with the residual added, and the residual projection (Linear +
+    layer_normalization, per frame) when the widths differ.  The update stack has no norm
+    layer, so its activations are not bounded: every matrix product here is an exact float32
+    one (the f32-input MFMA), never a two-term fp16 split."""
+
+    def __init__(self, blk, dtype, device):
+        if dtype != 'fp32':
+            raise NotImplementedError(f'graph attention runs in fp32 only, not {dtype!r}: the '
+                                      '16-bit paths have no attention kernel')
+        self.blk = blk
+        self.gat = blk.GATblk
+        self.device = torch.device(device)
+        self.dtype = dtype
+        upd = list(blk.upd)
+        if len(upd) < 2 or len(upd[0].block) != 2:
+            raise NotImplementedError('residual_graph_attn_block: an update stack of at least '
+                                      'two ffn_blocks without a norm layer is expected')
+        self.upd0 = upd[0].block[0]
+        self.upd0_act = upd[0].block[-1].kind
+        self.upd_tail = ChainPlan(specs_from_modules(upd[1:]), dtype, device)
+        self.res = (ChainPlan(specs_from_modules([blk.residual_connection]), dtype, device)
+                    if blk.residual_connection is not None else None)
+        for c in self.chains():   # the generic float32 chain: exact products, any range
+            c.use_fast = False
+            for p, _ in (c.pieces or []):
+                p.use_fast = False
+        self.c_in = self.gat.in_channels
+        self.d_extra = int(blk.in_extra_feature_dim or 0)
+        self.c_out = self.upd_tail.out_dim
+        self.use_fused = None   # None: fused when compiled for the shape; False: composed
+        self._ws = {}
+
+    def chains(self):
+        return [c for c in (self.upd_tail, self.res) if c is not None]
+
+    def refresh(self):
+        for c in self.chains():
+            c.refresh()
+
+    def invalidate(self):
+        for c in self.chains():
+            c.invalidate()
+
+    def run(self, x, e, g, x_out, extra=None, segs=None, alloc=None):
+        """x float32 [N, in], e float32 [E_cap, Ce] destination-major -> x_out [N, c_out]."""
+        N = x.shape[0]
+        dev = x.device
+        if alloc is None:
+            def alloc(name, shape, dtype):
+                return torch.empty(shape, dtype=dtype, device=dev)
+        gat = self.gat
+        HC = gat.heads * gat.out_channels
+        d = self.c_in + self.d_extra
+        with torch.no_grad():
+            cat = alloc(f'attn_cat{d + HC}', (N, d + HC), torch.float32)
+            cat[:, :self.c_in].copy_(x)               # (plumbing: the columns ahead of the
+            if self.d_extra:                          #  attention output)
+                cat[:, self.c_in:d].copy_(extra)
+            gat_v2_conv(gat, x, e, g, out=cat[:, d:], fused=self.use_fused, ws_cache=self._ws)
+            h = alloc(f'attn_h{self.upd0.out_features}', (N, self.upd0.out_features),
+                      torch.float32)
+            linear_f32(self.upd0.weight, self.upd0.bias, cat, h, act=self.upd0_act)
+            if self.res is not None:
+                ident = alloc(f'attn_id{self.c_out}', (N, self.c_out), torch.float32)
+                self.res(N, ident, x, x.shape[1], segs=segs)
+            else:
+                ident = x
+            self.upd_tail(N, x_out, h, h.shape[1], residual=ident, segs=segs)
+        return x_out
+
+
 class ModelPlans:
     """All chains of a Model_Inference for one compute dtype."""
 
@@ -1183,7 +1411,12 @@ class ModelPlans:
         mk = lambda mods: ChainPlan(specs_from_modules(mods), dtype, device)  # noqa: E731
         self.node_enc = mk(list(pred.encode_node_feat.encoder))
         self.edge_enc = mk(list(pred.encode_edge_feat.encoder))
-        self.convs = [ConvPlan(b, dtype, device) for b in pred.pass_messages.conv_blk]
+        from .gnn_attention import graph_attention
+        # pass_messages: the conv blocks, or (Model_Inference_v2) the attention blocks
+        attention = isinstance(pred.pass_messages, graph_attention)
+        blocks = list(pred.pass_messages.conv_blk)
+        self.convs = [] if attention else [ConvPlan(b, dtype, device) for b in blocks]
+        self.attn = [AttnPlan(b, dtype, device) for b in blocks] if attention else []
         pn, po, pl, pc = pred.predict_node, pred.predict_offset, pred.predict_link, pred.predict_class
         self.node_head = mk(list(pn.stem) + [pn.pred_cls.head[0], pn.pred_cls.head[1]])
         self.offset_head = mk(list(po.stem) + [po.pred_offsets.head[0], po.pred_offsets.head[1]])
@@ -1212,7 +1445,7 @@ class ModelPlans:
                             self.link_pre) if c is not None]
 
     def chains(self):
-        return self._heads() + [c for cv in self.convs for c in cv.chains()]
+        return self._heads() + [c for cv in self.convs + self.attn for c in cv.chains()]
 
     def link_pairs_pre(self, N, x, C, ucap, link, g) -> bool:
         """The link head through RG_IN_PAIRPRE: t = [stem ->] W0 x per node, then the pair
@@ -1239,11 +1472,11 @@ class ModelPlans:
         return True
 
     def refresh(self):
-        for p in self._heads() + self.convs:
+        for p in self._heads() + self.convs + self.attn:
             p.refresh()
 
     def invalidate(self):
-        for p in self._heads() + self.convs:
+        for p in self._heads() + self.convs + self.attn:
             p.invalidate()
 
 
@@ -1412,6 +1645,13 @@ def forward_batched(plans: ModelPlans, node_feats: torch.Tensor, edge_feats_dst:
         cv.upd(N, xn, x, C, mode=nat.IN_CONCAT2, in1=agg, w1=cv.c_msg, residual=ident,
                segs=segs('node'))
         x = xn
+    for li, ap in enumerate(plans.attn):   # Model_Inference_v2: attention blocks instead
+        xn = alloc(f'x{(li + 1) % 2}' if li + 1 < len(plans.attn) else 'xL', (N, ap.c_out), T)
+        if xn.data_ptr() == x.data_ptr():
+            xn = alloc('xalt', (N, ap.c_out), T)
+        mark('attention:start')
+        x = ap.run(x, e, g, xn, segs=segs('node'), alloc=alloc)
+        mark('attention:end')
     if coarse:
         if n_fused == len(plans.convs) and n_fused > 0:
             mark('conv_stack:end', True)
@@ -1620,6 +1860,57 @@ def run_conv_block(blk, node_features, edge_features, edge_index, dtype='fp32',
     out = torch.empty((N, cp.c_out), dtype=torch.float32, device=dev)
     cp.upd(N, out, x, x.shape[1], mode=nat.IN_CONCAT2, in1=xa, w1=d_extra + cp.c_msg,
            residual=ident)
+    return out
+
+
+def _edges_by_destination(edge_features, g: DeviceGraph) -> torch.Tensor:
+    """Reference-order edge rows -> destination-major float32 rows of a from_edge_index graph."""
+    ef = edge_features.float().contiguous()
+    E = g.n_edges
+    e = torch.empty((max(E, 1), ef.shape[1]), dtype=torch.float32, device=ef.device)
+    if E > 0:
+        nat.check(nat.lib().rg_gather_rows_f32(ef.data_ptr(), g.perm.data_ptr(), E, ef.shape[1],
+                                               e.data_ptr(), nat.stream_ptr(ef.device)),
+                  'rg_gather_rows_f32')
+    return e
+
+
+def run_gat_conv(gat, x, edge_index, edge_attr, fused: Optional[bool] = None) -> torch.Tensor:
+    """GATv2Conv.forward(x, edge_index, edge_attr) on one graph (reference edge order)."""
+    _require_device(x, 'x')
+    g = DeviceGraph.from_edge_index(edge_index, x.shape[0], count_pairs=False)
+    return gat_v2_conv(gat, x.float().contiguous(), _edges_by_destination(edge_attr, g), g,
+                       fused=fused)
+
+
+def run_attn_block(blk, node_features, edge_features, edge_index, dtype='fp32',
+                   extra_features=None, fused: Optional[bool] = None):
+    """residual_graph_attn_block.forward (gnn_attention.py:62-76) on one graph: the
+    single-block entry, as run_conv_block is for the conv block.  fused: as gat_v2_conv."""
+    _require_device(node_features, 'node_features')
+    dev = node_features.device
+    ap = cached_plan(blk, ('attn', dtype), lambda: AttnPlan(blk, dtype, dev))
+    N = node_features.shape[0]
+    g = DeviceGraph.from_edge_index(edge_index, N, count_pairs=False)
+    x = node_features.float().contiguous()
+    e = _edges_by_destination(edge_features, g)
+    extra = None
+    if blk.in_extra_feature_dim is not None:
+        if extra_features is None:
+            # reference: torch.concat((x, None, out)) raises
+            raise TypeError('expected Tensor as element 1 in argument 0, but got NoneType')
+        _require_device(extra_features, 'extra_features')
+        if tuple(extra_features.shape) != (N, blk.in_extra_feature_dim):
+            raise RuntimeError(f'extra_features of shape {tuple(extra_features.shape)}: the block '
+                               f'was built for [{N}, {blk.in_extra_feature_dim}]')
+        extra = extra_features.float()
+    out = torch.empty((N, ap.c_out), dtype=torch.float32, device=dev)
+    was = ap.use_fused
+    ap.use_fused = fused
+    try:
+        ap.run(x, e, g, out, extra=extra)
+    finally:
+        ap.use_fused = was
     return out
 
 

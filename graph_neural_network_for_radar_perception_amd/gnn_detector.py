@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import engine
+from .gnn_attention import graph_attention
 from .gnn_blocks import (graph_convolution, graph_feature_encoding, link_predictions,
                          node_offset_predictions, node_segmentation, object_classification)
 
@@ -306,6 +307,90 @@ class Model_Inference(nn.Module):
             raise UnboundLocalError("local variable 'cluster_members_list' referenced before "
                                     "assignment")
         return node_cls, node_reg, link_cls, obj_cls
+
+
+class Model_Inference_v2(nn.Module):
+    """gnn_detector.py:316-416: the detector whose message passing is ``graph_attention``
+    (GATv2 blocks of ``hidden_node_channels_GAT`` channels in ``num_heads_GAT`` heads) instead
+    of ``graph_convolution``.  Same constructor and ``forward`` signature as the reference,
+    same ``state_dict`` keys.  (The reference builds ``predict_offset`` without the norm
+    arguments its class requires, which raises; here it gets the configuration's, as in
+    ``Model_Inference``.)
+
+    Forward only and fp32 only: ``compute_dtype`` 'bf16' / 'fp16' raise NotImplementedError,
+    and the outputs carry no autograd graph whether or not autograd is enabled."""
+
+    def __init__(self, net_config):
+        super().__init__()
+        c = net_config
+        self.encode_node_feat = graph_feature_encoding(
+            c.input_node_feat_dim, c.node_feat_enc_stem_channels, c.activation, c.norm_layer,
+            c.num_groups)
+        self.encode_edge_feat = graph_feature_encoding(
+            c.input_edge_feat_dim, c.edge_feat_enc_stem_channels, c.activation, c.norm_layer,
+            c.num_groups)
+        self.pass_messages = graph_attention(
+            in_node_channels=c.node_feat_enc_stem_channels[-1],
+            in_edge_channels=c.edge_feat_enc_stem_channels[-1],
+            stem_channels=c.graph_convolution_stem_channels,
+            hidden_node_channels=c.hidden_node_channels_GAT, num_heads=c.num_heads_GAT,
+            activation=c.activation)
+        cl = c.graph_convolution_stem_channels[-1]
+        self.predict_node = node_segmentation(cl, c.node_pred_stem_channels, c.num_classes,
+                                              c.activation, c.norm_layer, c.num_groups)
+        self.predict_offset = node_offset_predictions(cl, c.node_pred_stem_channels,
+                                                      c.reg_offset_dim, c.activation,
+                                                      c.norm_layer, c.num_groups)
+        self.predict_link = link_predictions(cl, c.num_blocks_to_compute_edge,
+                                             c.link_pred_stem_channels, c.num_edge_classes,
+                                             c.activation, c.norm_layer, c.num_groups)
+        self.predict_class = object_classification(cl, c.node_pred_stem_channels, c.num_classes,
+                                                   c.activation, c.norm_layer, c.num_groups)
+        self.compute_dtype = 'fp32'
+        self._plans: Dict[str, engine.ModelPlans] = {}
+
+    def invalidate_plans(self):
+        """Re-pack every plan on next use (weights written outside torch)."""
+        for p in self._plans.values():
+            p.invalidate()
+
+    def plans(self, dtype: Optional[str] = None) -> engine.ModelPlans:
+        dtype = dtype or self.compute_dtype
+        if dtype != 'fp32':
+            raise NotImplementedError(f'Model_Inference_v2 runs in fp32 only, not {dtype!r}: the '
+                                      '16-bit paths have no attention kernel')
+        p = self._plans.get(dtype)
+        if p is None:
+            p = engine.ModelPlans(self, dtype, next(self.parameters()).device)
+            self._plans[dtype] = p
+        else:
+            p.refresh()
+        return p
+
+    @torch.no_grad()
+    def forward_frames(self, node_features: List[torch.Tensor], edge_features: List[torch.Tensor],
+                       edge_index: List[torch.Tensor],
+                       cluster_node_idx: List[List[torch.Tensor]]):
+        """Batched forward over several frames: per-batch concatenated (node_cls, node_reg,
+        link_cls, obj_cls), as Model_Inference.forward_frames returns them."""
+        engine._require_device(node_features[0], 'node_features')
+        nf, ef, ei, cptr, cidx, ncl, sizes = _batch_frames(node_features, edge_features,
+                                                           edge_index, cluster_node_idx)
+        g = engine.DeviceGraph.from_edge_index(ei, nf.shape[0])
+        _set_frames(g, sizes)
+        out = engine.forward_batched(self.plans(), nf, _edges_dst_major(ef, g), g, cptr, cidx,
+                                     ncl, n_pairs_cap=g.n_pairs)
+        return out.node_cls, out.node_reg, out.link_cls[:g.n_pairs], out.obj_cls
+
+    def forward(self, node_features: torch.Tensor, edge_features: torch.Tensor,
+                edge_index: torch.Tensor, adj_matrix: torch.Tensor,
+                cluster_node_idx: List[torch.Tensor],
+                augmented_features: Optional[torch.Tensor] = None):
+        """gnn_detector.py:395-416.  The link pairs come from edge_index (see
+        Model_Inference.forward); augmented_features is accepted and, as in the reference --
+        which builds graph_attention without extra-feature blocks -- not used."""
+        return self.forward_frames([node_features], [edge_features], [edge_index],
+                                   [cluster_node_idx])
 
 
 class Model_Training(nn.Module):

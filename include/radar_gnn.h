@@ -1367,6 +1367,50 @@ int rg_adamw_step_sched(float* param, const float* grad, float* exp_avg, float* 
                         int n_losses,
                         int* step_state, int parity, void* stream);
 
+/* ---------------------------------------------------------------- graph attention */
+
+/* One nn.Linear of any width on the f32-input MFMA (exact f32 products; the chain kernels
+ * and their packer stop at 256 features, the attention block's layers are up to 1024 wide):
+ *   out[r][o] = act(sum_k in[r][k] weight[o][k] + bias[o]),  r < rows, o < out_dim.
+ * weight: the float32 parameter where it lies, row-major [out_dim][ld_w] (no packed image);
+ * bias float32 [out_dim] or NULL; act RG_ACT_*; rows_dev: optional device int32 row count
+ * (`rows` is then the capacity).  Rows are independent of each other and of the launch
+ * shape; each sum runs in ascending k.  ld_* in floats. */
+int rg_linear_f32(const float* weight, int ld_w, const float* bias, int in_dim, int out_dim,
+                  int act, const float* in, int ld_in, long rows, const int* rows_dev, float* out,
+                  int ld_out, void* stream);
+
+/* GATv2Conv(in, C, heads = H, edge_dim = Ce, concat = True, add_self_loops = False,
+ * share_weights = False, bias = True), flow source -> target
+ * (modules/neural_net/gnn/gnn_attention.py:26-36), forward only, float32, after the two node
+ * projections:
+ *   m_k   = xl[src[k]] + xr[i] + e_k W_e^T                     k in segment i, [H][C]
+ *   a_kh  = sum_c att[h][c] leaky_relu(m_k[h][c], negative_slope)
+ *   w_kh  = exp(a_kh - max_k' a_k'h) / (sum_k' exp(a_k'h - max) + 1e-16)   over segment i
+ *   out_i = concat_h sum_k w_kh xl[src[k]][h][:] + bias                     [H C]
+ * Two launches: the logits [E][H] (e W_e^T on v_mfma_f32_32x32x2_f32, one wave per head with
+ * that head's W_e fragments in registers, the gathered rows as the accumulators' start), then
+ * one wave per destination: the segment's maximum, then the weights and the weighted rows in
+ * ascending edge position.  Nothing E x H C wide reaches memory, no atomics; a destination's
+ * result does not depend on the rest of the batch or on the launch shape.  A destination
+ * without incoming edges gets bias.
+ *   xlr      float32 [n_nodes][ld_xlr]: xl = columns [0, H C), xr = columns [H C, 2 H C)
+ *   e        float32 [n_edges_cap][ld_e], destination-major; positions from
+ *            seg_ptr[n_nodes] up to n_edges_cap are never read (e, src, dst alike)
+ *   seg_ptr  int32 [n_nodes + 1]; src, dst int32 [n_edges_cap]: the source and the owner of
+ *            each position (out-of-range indices are clamped to [0, n_nodes))
+ *   w_edge   lin_edge.weight where it lies, float32 [H C][ld_w]; att float32 [H C];
+ *            bias float32 [H C]
+ *   out      float32 [n_nodes][ld_out]
+ * Rows (xlr, e, w_edge, att, out: base and stride) must be 16-byte aligned.  Compiled for
+ * Ce = 64, C = 64, H = 8; any other shape: RG_ERR_UNSUPPORTED. */
+size_t rg_gat_v2_layer_workspace_size(long n_edges_cap, int heads);
+int rg_gat_v2_layer(const float* xlr, int ld_xlr, const float* e, int ld_e, const int* seg_ptr,
+                    const int* src, const int* dst, int n_nodes, long n_edges_cap,
+                    const float* w_edge, int ld_w, const float* att, const float* bias,
+                    int edge_dim, int heads, int head_dim, float negative_slope, float* out,
+                    int ld_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- diagnostics */
 
 /* Shader-clock calibration (bench.py; no product path calls it): n_blocks workgroups of
