@@ -776,9 +776,13 @@ __global__ void segmax_backward_kernel(const float* __restrict__ h, int ld_h, in
 }
 
 // ------------------------------------------------------------------ losses
-// log-sum-exp and argmax (first maximum) of a logit row
-__device__ __forceinline__ void row_stats(const float* x, int nc, float& lse, int& amax) {
-  float mx = x[0];
+// maximum, log sum exp(x - max) and argmax (first maximum) of a logit row.  The two parts of
+// the log-sum-exp stay apart: log_softmax is (x - mx) - ls, as torch evaluates it.  Added up,
+// mx + ls is rounded at the size of mx, and x - (mx + ls) carries that rounding whole: at logits
+// of 1e4 a softmax entry was 5e-4 off (two logits 1 apart: ulp(1e4) / 2 in the exponent)
+__device__ __forceinline__ void row_stats(const float* x, int nc, float& mx, float& ls,
+                                          int& amax) {
+  mx = x[0];
   amax = 0;
   for (int c = 1; c < nc; ++c)
     if (x[c] > mx) {
@@ -787,7 +791,7 @@ __device__ __forceinline__ void row_stats(const float* x, int nc, float& lse, in
     }
   float s = 0.f;
   for (int c = 0; c < nc; ++c) s += expf(x[c] - mx);
-  lse = mx + logf(s);
+  ls = logf(s);
 }
 
 // sigmoid_focal_loss (torchvision; alpha 0.25, gamma 2) of one logit and its 0/1 target,
@@ -827,11 +831,11 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(rg_loss_args a, double* 
       const int nc = a.n_classes;
       const float* x = term == 0 ? a.node_cls + (size_t)i * nc : a.obj + (size_t)i * nc;
       const int k = (int)(term == 0 ? a.node_class[i] : a.obj_class[i]);
-      float lse;
+      float mx, ls;
       int am;
-      row_stats(x, nc, lse, am);
+      row_stats(x, nc, mx, ls, am);
       const float w = term == 0 ? a.class_w[k] : 1.f;
-      sl += (double)(-(w * (x[k] - lse)));
+      sl += (double)(-(w * ((x[k] - mx) - ls)));
       sc += am == k;
     } else if (term == 1) {
       const float t0 = (a.node_offsets[2 * i] - a.mu_x) / a.sigma_x;
@@ -908,12 +912,13 @@ __global__ void loss_backward_kernel(rg_loss_args a, const float* __restrict__ g
       const float* x = term == 0 ? a.node_cls + (size_t)i * nc : a.obj + (size_t)i * nc;
       float* d = term == 0 ? dnc + (size_t)i * nc : dob + (size_t)i * nc;
       const int k = (int)(term == 0 ? a.node_class[i] : a.obj_class[i]);
-      float lse;
+      float mx, ls;
       int am;
-      row_stats(x, nc, lse, am);
+      row_stats(x, nc, mx, ls, am);
       const float w = term == 0 ? a.class_w[k] : 1.f;
       const float sc = term == 0 ? g0 * a.w_node_cls / (float)rows : g3 * a.w_obj_cls / (float)rows;
-      for (int c = 0; c < nc; ++c) d[c] = sc * w * (expf(x[c] - lse) - (c == k ? 1.f : 0.f));
+      for (int c = 0; c < nc; ++c)
+        d[c] = sc * w * (expf((x[c] - mx) - ls) - (c == k ? 1.f : 0.f));
     } else if (term == 1) {
       const float t0 = (a.node_offsets[2 * i] - a.mu_x) / a.sigma_x;
       const float t1 = (a.node_offsets[2 * i + 1] - a.mu_y) / a.sigma_y;
